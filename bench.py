@@ -27,6 +27,11 @@ cpu_baseline: the oracle (-O3 restatement, kind "port") or oracle/_ref (the refe
 
 Other workloads (--workload fft4096 | fmchain | rotate | abs | freq_demod | direct255 | decim8 | interp4 | fir255_i16) print the same kind of line
 for the secondary configs; the driver uses the default.
+
+A plain run sets up, warms up, times the K steps and prints the line: `roofline` is priced on the timed region's own HIP events.
+--full adds what takes time or runs of its own beside that: the CPU baselines, roofline.sustained / .cold / .clock_mhz_under_load and
+(default workload, N = 1) the `secondary` object; --no-cpu, --no-secondary, --no-cold and --sustain then trim it as before.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs: a seeded sample of a large output).
 """
 import argparse
 import json
@@ -45,6 +50,9 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # datasheet FP64 vector: 256 CUs x 4 SIMDs x 16 lanes x 2 flop x 2.4 GHz
 SHARD = 64 * 1024 * 1024       # samples per GPU (configs[1])
 PREWARM = 400                  # untimed setup passes before the W warm-up steps (clock settling: tools/transient_probe.py)
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_EDGE_ROWS = 1 << 16       # ... of an output larger than that: its first and last rows
+DUMP_SAMPLE_ROWS = 2 << 20     # ... and a seeded sample of rows from all of it
 
 
 def parse():
@@ -87,7 +95,19 @@ def parse():
     ap.add_argument("--no-cold", action="store_true", help="skip roofline.cold (three bursts of 20 launches behind 5 ms of idle)")
     ap.add_argument("--settle", type=int, default=PREWARM,
                     help="untimed setup passes before the W warm-up steps (clock settling after idle; reported as config.setup_passes)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: CPU baselines, sustained / cold / clock-under-load figures and, for "
+                         "the default workload on one GPU, the `secondary` object.  Off: the run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; a fixed, seeded sample of outputs "
+                         "larger than %d MiB in all)" % (DUMP_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.settle < 0:
+        ap.error("--steps must be >= 1, --warmup and --settle >= 0")
+    if not args.full:
+        args.no_cpu = args.no_secondary = args.no_cold = True
+        args.sustain = 0.0
+    return args
 
 
 def _flush_c_stdio():
@@ -116,6 +136,44 @@ def _host_cores():
     except AttributeError:
         n = os.cpu_count() or 1
     return max(1, min(n, 64))
+
+
+def dump_outputs(dirname, name, out, world=1):
+    """--dump-outputs: the array the timed path handed its caller in the last timed step -> dirname/<name>*.npy, float32 (float64 stays
+    float64; the integer types are exact in float32).  Within DUMP_BYTES / world it is written whole as <name>.npy; a larger one as
+    <name>_head / <name>_tail (its first and last DUMP_EDGE_ROWS rows) and <name>_sample: one row from each of DUMP_SAMPLE_ROWS equal
+    strata, drawn by a generator seeded with 0, the row numbers beside it in <name>_sample_index (float64).  The sample depends on the
+    output's shape alone, so two builds fed the same inputs write comparable files.  Returns the paths written."""
+    import numpy as np
+    import torch
+
+    def host(t):
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float32)
+        return t.cpu().numpy()
+
+    os.makedirs(dirname, exist_ok=True)
+    if out.is_cuda:
+        torch.cuda.synchronize(out.device)
+    rows = out.shape[0]
+    row_bytes = max(1, out[:1].numel()) * (8 if out.dtype == torch.float64 else 4)
+    budget = DUMP_BYTES // world
+    if rows * row_bytes <= budget:
+        arrays = {name: host(out)}
+    else:
+        edge = min(DUMP_EDGE_ROWS, rows // 4)
+        n = min(DUMP_SAMPLE_ROWS, (budget - 2 * edge * row_bytes) // (row_bytes + 8))
+        bounds = np.arange(n + 1, dtype=np.int64) * rows // n
+        idx = bounds[:-1] + (np.random.default_rng(0).random(n) * (bounds[1:] - bounds[:-1])).astype(np.int64)
+        arrays = {name + "_head": host(out[:edge]), name + "_tail": host(out[rows - edge:]),
+                  name + "_sample": host(out.index_select(0, torch.from_numpy(idx).to(out.device))),
+                  name + "_sample_index": idx.astype(np.float64)}
+    paths = []
+    for k, a in arrays.items():
+        paths.append(os.path.join(dirname, k + ".npy"))
+        np.save(paths[-1], a)
+    return paths
 
 
 def cpu_baseline_fir(taps, seed, nsamples, real_taps=False, real_stream=False):
@@ -401,6 +459,8 @@ def run_native(args):
     from pothoscomms_amd import _lib, device, taps as tp
     if args.workload not in ("fir255", "fmchain"):
         raise SystemExit("--driver native runs the sharded workloads: fir255, fmchain")
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs: the ranks driver (the default) only")
     L = _lib.load()
     ndev = torch.cuda.device_count()
     G = args.gpus
@@ -546,6 +606,7 @@ class Workload:
     blocks = None              # overlap-save blocks per launch (for valu.per_wave_block)
     owner = None               # the ShardedFir / ShardedFmChain, when the stream is sharded over ranks
     inputs = ()                # the device tensors the step reads (tools/floor_table.py zeroes them for the "kernel on zeros" row)
+    output = None              # last step's return value -> the array a caller of the path receives (None: the step returns it itself)
 
 
 PIPELINED = ("; software-pipelined over two input buffers: the halo of batch k+1 is exchanged while batch k is filtered -- one exchange and one "
@@ -605,6 +666,7 @@ def build_workload(wl, C, dev, rank, world, args):
         W.read_bytes = 8.0 * W.units
         W.kernel_name = "fft_r16_kernel<12>"
         W.step = lambda: fft.transform_dev(x, y, nframes)
+        W.output = lambda last: y
         W.inputs = (x,)
         W.desc = {"workload": "4096-pt complex_float32 FFT (/comms/fft), 65536 frames per GPU", "frames": nframes}
         W.metric = "Msamples/s complex_float32 4096-pt FFT"
@@ -636,6 +698,7 @@ def build_workload(wl, C, dev, rank, world, args):
             y = torch.empty((n,), dtype=torch.float32, device=dev)
             device.fill_uniform_f32_dev(x, seed=5, offset=0)
             W.step = lambda: ch.process_dev(x, y, n + 126, n)
+            W.output = lambda last: y
             W.inputs = (x,)
         W.units = n
         W.roof_bytes = 12.0 * n
@@ -667,6 +730,7 @@ def build_workload(wl, C, dev, rank, world, args):
         W.read_bytes = 8.0 * n
         W.kernel_name = "fir_cf32_ols4096_decim_batched_kernel" if wl == "decim8" else "fir_cf32_ols4096_interp_batched_kernel"
         W.step = lambda: f.process_dev(x, y)
+        W.output = lambda last: y[:n * L // M]
         W.inputs = (x,)
         W.desc = {"workload": "255-tap complex_float32 FIR, %s, %d input samples per GPU" %
                               ("decimation 8 folded into the spectrum (input rate)" if wl == "decim8"
@@ -684,13 +748,15 @@ def build_workload(wl, C, dev, rank, world, args):
         f = device.FirFilter("complex_int16", "COMPLEX")
         f.set_taps(h)
         K = f.K
-        x = torch.randint(-20000, 20000, (n + K - 1, 2), device=dev).to(torch.int16)
+        gen = torch.Generator(device=dev).manual_seed(11)      # the same stream from run to run (--dump-outputs compares builds)
+        x = torch.randint(-20000, 20000, (n + K - 1, 2), device=dev, generator=gen).to(torch.int16)
         y = torch.empty((n, 2), dtype=torch.int16, device=dev)
         W.units = n
         W.roof_bytes = 8.0 * n
         W.read_bytes = 4.0 * n
         W.kernel_name = "fir_cf64_ip_kernel"
         W.step = lambda: f.process_dev(x, y)
+        W.output = lambda last: y
         W.inputs = (x,)
         W.desc = {"workload": "255-tap complex_int16 FIR (bit-exact, double-precision overlap-save), %d samples per GPU" % n, "taps": 255}
         W.metric = "Msamples/s complex_int16 255-tap FIR"
@@ -722,6 +788,7 @@ def build_workload(wl, C, dev, rank, world, args):
         W.read_bytes = 4.0 * n
         W.kernel_name = "fir_cf32_upols_kernel"
         W.step = lambda: f.process_dev(x, y)
+        W.output = lambda last: y
         W.inputs = (x,)
         W.desc = {"workload": "%d-tap float32 FIR (real stream, real taps), two halves of the call as one complex stream through the "
                               "partitioned kernel, %d samples per GPU" % (K, n), "taps": K}
@@ -748,6 +815,7 @@ def build_workload(wl, C, dev, rank, world, args):
         W.read_bytes = 8.0 * n
         W.kernel_name = "fir_cf32_upols_kernel"
         W.step = lambda: f.process_dev(x, y)
+        W.output = lambda last: y
         W.inputs = (x,)
         W.desc = {"workload": "%d-tap complex_float32 FIR, 4096-sample overlap-save blocks with the taps in %d partitions, %d samples per GPU"
                               % (K, (K - 1 + 2047) // 2048, n), "taps": K}
@@ -773,6 +841,7 @@ def build_workload(wl, C, dev, rank, world, args):
             W.kernel_name = "freqdemod_kernel"
             W.step = lambda: fd.process_dev(x, y, n)
             W.owner_keepalive = fd
+        W.output = lambda last: y
         W.inputs = (x,)
         W.desc = {"workload": "/comms/%s complex_float32 -> float32, %d samples" % (wl, n)}
         W.metric = "Msamples/s complex_float32 %s" % wl
@@ -786,6 +855,7 @@ def build_workload(wl, C, dev, rank, world, args):
         W.read_bytes = 8.0 * n
         W.kernel_name = "map_kernel<rotate>"
         W.step = lambda: device.rotate(x, 0.7, scalar=device.F32, out=y, n=n)
+        W.output = lambda last: y
         W.inputs = (x,)
         W.desc = {"workload": "/comms/rotate complex_float32, %d samples" % n}
         W.metric = "Msamples/s complex_float32 rotate"
@@ -1477,7 +1547,7 @@ def main():
     def timed_region():
         """EXACTLY K steps between barrier + synchronize on both sides -> (wall seconds, max over ranks; ms per launch from ONE pair of HIP
         events on the launch stream around the K steps: no event packet between two launches -- a pair per step costs ~12 us of gap per
-        step on this stack)."""
+        step on this stack).  With --dump-outputs, what the last step computed is written behind the clock."""
         # (torch creates the HIP event behind an Event object at its FIRST record(): created here, not between the clock reading and the
         # first timed launch -- at the driver's --steps 20 the two creations read as 1-3 % of the region, tools/wall_vs_events.py)
         ev0.record()
@@ -1486,7 +1556,7 @@ def main():
         t0 = time.perf_counter()
         ev0.record()
         for k in range(args.steps):
-            step()
+            last = step()
         ev1.record()
         barrier()
         wall = time.perf_counter() - t0
@@ -1495,6 +1565,10 @@ def main():
             t = torch.tensor([wall], dtype=torch.float64, device=ctl)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             wall = float(t.item())
+        if args.dump_outputs:
+            # every rank its own shard; a fall-back that re-times the steps writes them again
+            dump_outputs(args.dump_outputs, W.name if world == 1 else "%s_rank%d" % (W.name, rank),
+                         last if W.output is None else W.output(last), world)
         return wall, span_ms
 
     elapsed, span_ms = timed_region()

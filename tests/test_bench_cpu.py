@@ -77,6 +77,59 @@ def test_default_line_documents_itself():
     assert (a.gpus, a.steps, a.warmup, a.no_secondary, a.no_cold, a.workload) == (1, 20, 5, True, True, "fir255")
 
 
+def _parse(*argv):
+    sys_argv, sys.argv = sys.argv, ["bench.py"] + list(argv)
+    try:
+        return bench.parse()
+    finally:
+        sys.argv = sys_argv
+
+
+def test_a_plain_run_leaves_everything_beside_the_headline_to_full():
+    """the plain run times the steps and prints the line; the CPU baselines, sustained / cold / clock figures and `secondary` come with --full,
+    where the switches that trim them work as before"""
+    a = _parse("--gpus", "1", "--steps", "7", "--warmup", "3")
+    assert (a.full, a.steps, a.warmup, a.dump_outputs) == (False, 7, 3, None)
+    assert a.no_cpu and a.no_secondary and a.no_cold and a.sustain == 0
+    a = _parse("--full")
+    assert a.full and not a.no_cpu and not a.no_secondary and not a.no_cold and a.sustain == 1.0
+    a = _parse("--full", "--no-cpu", "--sustain", "0.5", "--dump-outputs", "d")
+    assert a.no_cpu and not a.no_secondary and a.sustain == 0.5 and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        _parse("--steps", "0")
+
+
+def test_dump_outputs_whole_sampled_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: a small output whole; a large one as head, tail and a seeded sample of rows with their row numbers, within the byte
+    budget; float32 / float64 files only, the same files for the same output"""
+    import numpy as np
+    import torch
+    y = torch.arange(2 * 1000, dtype=torch.float32).reshape(-1, 2)
+    paths = bench.dump_outputs(str(tmp_path / "a"), "small", y)
+    assert [os.path.basename(p) for p in paths] == ["small.npy"] and np.array_equal(np.load(paths[0]), y.numpy())
+    i16 = torch.arange(-500, 500, dtype=torch.int16).reshape(-1, 2)
+    got = np.load(bench.dump_outputs(str(tmp_path / "a"), "i16", i16)[0])
+    assert got.dtype == np.float32 and np.array_equal(got, i16.numpy().astype(np.float32))
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    monkeypatch.setattr(bench, "DUMP_EDGE_ROWS", 256)
+    big = torch.randn((100000, 2), dtype=torch.float32, generator=torch.Generator().manual_seed(1))
+    runs = []
+    for d in ("b", "c"):
+        paths = bench.dump_outputs(str(tmp_path / d), "big", big)
+        runs.append({os.path.basename(p): np.load(p) for p in paths})
+        assert sum(os.path.getsize(p) for p in paths) <= (64 << 10) + 4 * 128          # (npy headers)
+    a, b = runs
+    assert set(a) == {"big_head.npy", "big_tail.npy", "big_sample.npy", "big_sample_index.npy"}
+    assert all(np.array_equal(a[k], b[k]) for k in a) and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    idx = a["big_sample_index.npy"]
+    assert idx.dtype == np.float64 and len(idx) > 1000 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 100000
+    assert np.array_equal(a["big_sample.npy"], big.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(a["big_head.npy"], big.numpy()[:256]) and np.array_equal(a["big_tail.npy"], big.numpy()[-256:])
+    half = bench.dump_outputs(str(tmp_path / "r"), "big_rank1", big, world=2)      # each of N ranks keeps to 1/N of the budget
+    assert sum(os.path.getsize(p) for p in half) <= (32 << 10) + 4 * 128
+
+
 def _committed_line(name):
     p = os.path.join(ROOT, "profiles", "r06", name)
     if not os.path.exists(p):

@@ -395,6 +395,19 @@ def test_supervised_bench_a_gate_timeout_in_setup_switches_every_rank_to_two_lau
     assert any("a gated launch timed out" in w for w in c["fallback_reason"]) and "retimed" not in c
 
 
+def test_supervised_bench_every_rank_dumps_what_its_last_timed_step_computed(tmp_path):
+    """--dump-outputs at N > 1: each rank writes its own shard's output of the last timed step, named after its rank"""
+    import numpy as np
+    r, lines = _bench_standin({}, "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    _is_flagged_standin_line(lines[0], 2)
+    assert lines[0]["steps"] == 3
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["fir255_rank0.npy", "fir255_rank1.npy"]
+    y0, y1 = (np.load(tmp_path / ("fir255_rank%d.npy" % k)) for k in (0, 1))
+    assert y0.dtype == np.float32 and y0.shape == y1.shape == (8192, 2) and np.isfinite(y0).all() and np.isfinite(y1).all()
+    assert not np.array_equal(y0, y1)
+
+
 def test_supervised_bench_a_gate_timeout_behind_the_timed_region_is_retimed_not_deadlocked():
     """ONE rank > 0 finds a gate timeout behind the timed region.  It still takes part in the seam check (a collective step of
     the ring), every rank learns of the finding, all switch to the two-launch form, the K steps are timed again and the line says so --

@@ -305,6 +305,36 @@ def test_bench_native_driver_rehearsed_on_one_gpu_and_refused_without_enough_gpu
     assert line["metric"].startswith("Msamples/s fused FM-demod chain") and line["config"]["halo_samples"] == 127
 
 
+def test_bench_plain_run_times_k_steps_and_dumps_what_the_last_one_computed(tmp_path, oracle):
+    """`bench.py --steps K` times K steps and says so; the plain line carries the headline fields and none of what --full adds;
+    --dump-outputs writes the last timed step's output of the 64 Mi-sample headline FIR -- head, tail and a seeded sample, within
+    64 MiB -- and its head is the oracle's FIR of the same counter-hash stream"""
+    import json
+
+    from pothoscomms_amd import taps as tp
+    r = _run_bench({}, "--steps", "7", "--warmup", "2", "--settle", "5", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert (line["unit"], line["higher_is_better"], line["dtype"]) == ("Msamples/s", True, "f32")
+    assert "cpu_baseline" not in line and "secondary" not in line
+    assert not {"sustained", "cold", "clock_mhz_under_load"} & set(line["roofline"])
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["fir255_head.npy", "fir255_sample.npy", "fir255_sample_index.npy", "fir255_tail.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    head, idx, sample = (np.load(tmp_path / f) for f in ("fir255_head.npy", "fir255_sample_index.npy", "fir255_sample.npy"))
+    assert head.dtype == np.float32 and head.shape == (1 << 16, 2) and idx.dtype == np.float64 and sample.shape == (len(idx), 2)
+    h = tp.c1_taps()
+    K, m = len(h), head.shape[0]
+    ref_blk = oracle.Fir(oracle.F32, True, True)
+    ref_blk.set_taps(h)
+    ref_blk.activate()
+    want, _, _, _ = ref_blk.work(oracle.fill_uniform_f32(2 * (m + K - 1), 2, 0).reshape(-1, 2), m)
+    assert nerr(head, want) <= TOL
+    first = idx < m                                                    # sampled rows inside the head are the head's rows
+    assert first.any() and np.array_equal(sample[first], head[idx[first].astype(np.int64)])
+
+
 # ---- the RCCL branch of the rank driver, for real, on ONE GPU: a group of one rank whose ring sends the halo to the rank itself ----
 
 def _rccl_self_worker(port, C, chain, q, two_launch=False):

@@ -4,9 +4,9 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/r05z}; rm -rf $O; mkdir -p $O
 ulimit -c 0
 make -s -C tools ubench ols_lab3 clk_lab floor_lab pcie_lab > /dev/null 2>&1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> /dev/null
-for w in fft4096 fmchain rotate direct255 decim8 interp4 fir255_i16; do python bench.py --workload $w 2>/dev/null | tail -1 >> $O/bench_other_workloads.jsonl; done
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> /dev/null
+for w in fft4096 fmchain rotate direct255 decim8 interp4 fir255_i16; do python bench.py --full --workload $w 2>/dev/null | tail -1 >> $O/bench_other_workloads.jsonl; done
 PCX_BENCH_BACKEND=gloo python bench.py --gpus 2 --shard 33554432 --steps 50 --warmup 10 --no-cpu > $O/bench_two_ranks_one_gpu_gloo.json 2> /dev/null
 python bench.py --driver native --gpus 2 --native-devices 0,0 --shard 33554432 --no-cpu > $O/bench_native_two_shards_one_gpu.json 2> /dev/null
 python bench.py --driver native --gpus 2 --native-devices 0,0 --shard 33554432 --workload fmchain --no-cpu > $O/bench_native_two_shards_one_gpu_fmchain.json 2> /dev/null
@@ -18,11 +18,11 @@ python bench.py --driver native --gpus 2 --native-devices 0,0 --shard 33554432 -
 PCX_BENCH_BACKEND=gloo python bench.py --gpus 8 --shard 8388608 --steps 50 --warmup 10 --no-cpu > $O/bench_eight_ranks_one_gpu_gloo.json 2> /dev/null
 # the pass of a MIDDLE rank of an RCCL world on this one GPU (halo sent to the rank itself): plain, pipelined (the N > 1 default), unpipelined
 for w in fir255 fmchain; do s=""; [ $w = fmchain ] && s="_fmchain"
-  python bench.py --workload $w --no-cpu --no-secondary 2>/dev/null | tail -1 > $O/bench_rccl_rank_rehearsal_plain_same_box$s.json
-  python bench.py --workload $w --no-cpu --no-secondary --rehearse-rccl-rank --no-autotune 2>/dev/null | tail -1 > $O/bench_rccl_rank_rehearsal$s.json
-  python bench.py --workload $w --no-cpu --no-secondary --rehearse-rccl-rank --no-pingpong 2>/dev/null | tail -1 > $O/bench_rccl_rank_rehearsal_unpipelined$s.json
+  python bench.py --full --workload $w --no-cpu --no-secondary 2>/dev/null | tail -1 > $O/bench_rccl_rank_rehearsal_plain_same_box$s.json
+  python bench.py --full --workload $w --no-cpu --no-secondary --rehearse-rccl-rank --no-autotune 2>/dev/null | tail -1 > $O/bench_rccl_rank_rehearsal$s.json
+  python bench.py --full --workload $w --no-cpu --no-secondary --rehearse-rccl-rank --no-pingpong 2>/dev/null | tail -1 > $O/bench_rccl_rank_rehearsal_unpipelined$s.json
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_kt -- python3 bench.py --steps 2000 --warmup 50 --no-cpu > $O/bench_kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_kt -- python3 bench.py --full --steps 2000 --warmup 50 --no-cpu > $O/bench_kt.log 2>&1
 bash tools/prof.sh fir255 $O/fir255 ols4096 > /dev/null 2>&1
 bash tools/prof.sh fft4096 $O/fft4096 fft_r16 > /dev/null 2>&1
 bash tools/prof.sh fmchain $O/fmchain fmchain > /dev/null 2>&1
