@@ -306,6 +306,28 @@ PCX_API int pcx_freqdemod_process(pcx_freqdemod *h, const void *in, void *out, s
 PCX_API int pcx_freqdemod_process_dev(pcx_freqdemod *h, const void *in_dev, void *out_dev, size_t n, void *stream);
 
 /* ===================================================================== *
+ *  /comms/dc_removal      filter/DCRemoval.cpp, filter/MovingAverage.hpp
+ * ===================================================================== */
+typedef struct pcx_dcremoval pcx_dcremoval;
+/* DCRemovalFactory(dtype), DCRemoval.cpp:121-136: scalar in {F64, F32, I64, I32, I16, I8}, real or complex; the accumulator types
+ * are the reference's (f64, f32, i64, i64, i32, i16, complex alike).  Created at average size 512, cascade size 2. */
+PCX_API int pcx_dcremoval_create(int scalar, int is_complex, pcx_dcremoval **out);
+PCX_API int pcx_dcremoval_destroy(pcx_dcremoval *h);
+/* setAverageSize / setCascadeSize (DCRemoval.cpp:57-79): zero -> PCX_ERR_ARG; every stage starts over.  The device state and
+ * workspace are allocated here, never in a process call. */
+PCX_API int pcx_dcremoval_set_sizes(pcx_dcremoval *h, size_t average_size, size_t cascade_size);
+PCX_API int pcx_dcremoval_get_sizes(const pcx_dcremoval *h, size_t *average_size, size_t *cascade_size);
+/* activate(): every stage's history and accumulator back to zero */
+PCX_API int pcx_dcremoval_reset(pcx_dcremoval *h);
+/* the loop DCRemoval.cpp:100-110 over n elements, state carried across calls.  Integer types are bit-exact with the reference
+ * compiled for x86-64; float types are computed without the reference's drift (DESIGN.md 9 gives the bounds).  A divisor that the
+ * accumulator type narrows to zero (the reference divides by zero there) -> PCX_ERR_ARG, nothing launched, out untouched: complex_int8
+ * at average sizes that are multiples of 256, complex_int16 at multiples of 65536, int8 at multiples of 65536.  After a set_sizes that
+ * failed to allocate, every call but set_sizes and destroy -> PCX_ERR_STATE. */
+PCX_API int pcx_dcremoval_process(pcx_dcremoval *h, const void *in, void *out, size_t n);
+PCX_API int pcx_dcremoval_process_dev(pcx_dcremoval *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

@@ -107,6 +107,13 @@ SIGNATURES = {
     "pcx_freqdemod_reset": (_i, [_vp]),
     "pcx_freqdemod_process": (_i, [_vp, _vp, _vp, _sz]),
     "pcx_freqdemod_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_dcremoval_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "pcx_dcremoval_destroy": (_i, [_vp]),
+    "pcx_dcremoval_set_sizes": (_i, [_vp, _sz, _sz]),
+    "pcx_dcremoval_get_sizes": (_i, [_vp, _psz, _psz]),
+    "pcx_dcremoval_reset": (_i, [_vp]),
+    "pcx_dcremoval_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_dcremoval_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

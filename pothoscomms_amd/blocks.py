@@ -27,14 +27,24 @@ class PcxbLabel(C.Structure):
 
 
 _blib = None
+# the module libraries: "comms" is libpcx_blocks.so (comms_blocks.cpp, fir_designer.cpp), "filter" libpcx_filter_blocks.so
+# (filter_blocks.cpp: /comms/dc_removal) -- one registry each, as Pothos loads one module library per source directory
+MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so")}
+_mlibs = {}
 
 
-def load():
+def load(module="comms"):
     global _blib
-    if _blib is not None:
+    if module == "comms" and _blib is not None:
         return _blib
+    if module in _mlibs:
+        return _mlibs[module]
     _lib.load()    # one HIP runtime per process, libpcx_hip.so first
-    path = os.environ.get("PCX_BLOCKS_LIBRARY") or BLOCKS_LIB_PATH     # the override selects the sanitizer build (make asan)
+    if module not in MODULES:
+        raise ValueError("no block module %r (%s)" % (module, ", ".join(sorted(MODULES))))
+    path = MODULES[module]
+    if module == "comms":
+        path = os.environ.get("PCX_BLOCKS_LIBRARY") or path     # the override selects the sanitizer build (make asan)
     if not os.path.exists(path):
         raise ImportError("%s is missing: build with make -C pothoscomms_amd/csrc" % path)
     L = C.CDLL(path)
@@ -80,14 +90,21 @@ def load():
     L.pcxb_work_ports.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.pcxb_work.argtypes = [vp, vp, sz, C.POINTER(PcxbLabel), sz, vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                             C.POINTER(PcxbLabel), sz, C.POINTER(sz)]
-    _blib = L
+    if module == "comms":
+        _blib = L
+    else:
+        _mlibs[module] = L
     return L
 
 
 def _check(rc):
+    _check_in("comms", rc)
+
+
+def _check_in(module, rc):
     if rc == 0:
         return
-    msg = load().pcxb_last_error().decode("utf-8", "replace")
+    msg = load(module).pcxb_last_error().decode("utf-8", "replace")
     if rc == _lib.ERR_ARG:
         raise _lib.InvalidArgument(rc, msg)
     if rc == _lib.ERR_UNSUPPORTED:
@@ -100,9 +117,15 @@ def registry_paths():
     return sorted(L.pcxb_registry_path(i).decode() for i in range(L.pcxb_registry_count()))
 
 
-def registry_arity(path):
+def registry_arity(path, module="comms"):
     """how many arguments the factory registered at `path` takes (-1: no such path)"""
-    return int(load().pcxb_registry_arity(path.encode()))
+    return int(load(module).pcxb_registry_arity(path.encode()))
+
+
+def module_registry_paths(module):
+    """the registry of one module library (registry_paths() is the "comms" module's)"""
+    L = load(module)
+    return sorted(L.pcxb_registry_path(i).decode() for i in range(L.pcxb_registry_count()))
 
 
 class Label:
@@ -142,8 +165,9 @@ class Label:
 
 
 class Block:
-    def __init__(self, path, dtype, *args, dimension=1):
-        L = load()
+    def __init__(self, path, dtype, *args, dimension=1, module="comms"):
+        self._module = module
+        L = load(self._module)
         self.path = path
         self.dtype = dtype
         sarg, nbins, inverse = None, 0, 0
@@ -152,7 +176,7 @@ class Block:
         elif path == "/comms/fft":
             nbins, inverse = int(args[0]), int(bool(args[1])) if len(args) > 1 else 0
         self._h = C.c_void_p()
-        _check(L.pcxb_make(path.encode(), (dtype or "").encode(), dimension, sarg, nbins, inverse, C.byref(self._h)))
+        _check_in(self._module, L.pcxb_make(path.encode(), (dtype or "").encode(), dimension, sarg, nbins, inverse, C.byref(self._h)))
         self._slots = []          # blocks wired to this one's signals: kept alive as long as it can emit
         if path.endswith("fir_designer"):     # no stream ports: a signal source only
             self.in_dtype = self.out_dtype = None
@@ -163,7 +187,7 @@ class Block:
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            load().pcxb_destroy(self._h)
+            load(self._module).pcxb_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -175,90 +199,91 @@ class Block:
     def _port(self, is_output):
         name = C.create_string_buffer(64)
         dim, nbytes = C.c_size_t(), C.c_size_t()
-        _check(load().pcxb_port_dtype(self._h, is_output, name, 64, C.byref(dim), C.byref(nbytes)))
+        _check_in(self._module, load(self._module).pcxb_port_dtype(self._h, is_output, name, 64, C.byref(dim), C.byref(nbytes)))
         return name.value.decode(), dim.value, nbytes.value
 
     # ---- registered calls ----
     def call(self, name, *args):
-        L, n = load(), name.encode()
+        L, n = load(self._module), name.encode()
         if name == "setTaps":
             t = np.asarray(args[0])
             cplx = np.iscomplexobj(t)
             flat = np.ascontiguousarray(t.astype(np.complex128)).view(np.float64) if cplx else np.ascontiguousarray(t.astype(np.float64))
-            return _check(L.pcxb_call_taps(self._h, n, flat.ctypes.data_as(C.c_void_p), t.size, int(cplx)))
+            return _check_in(self._module, L.pcxb_call_taps(self._h, n, flat.ctypes.data_as(C.c_void_p), t.size, int(cplx)))
         if name == "getTaps":
             cplx = bool(args[0]) if args else False
             buf = np.zeros(1 << 16, np.float64)
             cnt = C.c_size_t()
-            _check(L.pcxb_get_taps(self._h, n, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(cnt), int(cplx)))
+            _check_in(self._module, L.pcxb_get_taps(self._h, n, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(cnt), int(cplx)))
             return buf[:2 * cnt.value].view(np.complex128).copy() if cplx else buf[:cnt.value].copy()
         if name in ("setWindowArgs", "setFrequencies"):      # std::vector<double>
             flat = np.ascontiguousarray(np.asarray(args[0], dtype=np.float64))
-            return _check(L.pcxb_call_taps(self._h, n, flat.ctypes.data_as(C.c_void_p), flat.size, 0))
+            return _check_in(self._module, L.pcxb_call_taps(self._h, n, flat.ctypes.data_as(C.c_void_p), flat.size, 0))
         if name == "windowArgs":
             buf, cnt = np.zeros(64, np.float64), C.c_size_t()
-            _check(L.pcxb_get_taps(self._h, n, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(cnt), 0))
+            _check_in(self._module, L.pcxb_get_taps(self._h, n, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(cnt), 0))
             return buf[:cnt.value].copy()
         if name in ("setPreload", "setDevices"):
             v = (C.c_size_t * max(1, len(args[0])))(*[int(a) for a in args[0]])
-            return _check(L.pcxb_call_sizes(self._h, n, v, len(args[0])))
+            return _check_in(self._module, L.pcxb_call_sizes(self._h, n, v, len(args[0])))
         if name in ("preload", "getDevices"):
             v, cnt = (C.c_size_t * 64)(), C.c_size_t()
-            _check(L.pcxb_get_sizes(self._h, n, v, 64, C.byref(cnt)))
+            _check_in(self._module, L.pcxb_get_sizes(self._h, n, v, 64, C.byref(cnt)))
             return [int(v[k]) for k in range(cnt.value)]
         if not args:   # getter
-            if name in ("getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes"):
+            if name in ("getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
+                        "getAverageSize", "getCascadeSize"):
                 v = C.c_size_t()
-                _check(L.pcxb_get_size(self._h, n, C.byref(v)))
+                _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value
             if name in ("getWaitTaps",):
                 v = C.c_int()
-                _check(L.pcxb_get_bool(self._h, n, C.byref(v)))
+                _check_in(self._module, L.pcxb_get_bool(self._h, n, C.byref(v)))
                 return bool(v.value)
             if name in ("getPhase", "getFactor", "sampleRate", "frequencyLower", "frequencyUpper", "bandwidthTrans", "alpha",
                         "stopDB", "passDB", "gain"):
                 v = C.c_double()
-                _check(L.pcxb_get_double(self._h, n, C.byref(v)))
+                _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
                 return v.value
             s = C.create_string_buffer(128)
-            _check(L.pcxb_get_string(self._h, n, s, 128))
+            _check_in(self._module, L.pcxb_get_string(self._h, n, s, 128))
             return s.value.decode()
         a = args[0]
         if isinstance(a, bool):
-            return _check(L.pcxb_call_bool(self._h, n, int(a)))
+            return _check_in(self._module, L.pcxb_call_bool(self._h, n, int(a)))
         if isinstance(a, (int, np.integer)):
-            return _check(L.pcxb_call_size(self._h, n, int(a)))
+            return _check_in(self._module, L.pcxb_call_size(self._h, n, int(a)))
         if isinstance(a, float):
-            return _check(L.pcxb_call_double(self._h, n, a))
-        return _check(L.pcxb_call_string(self._h, n, str(a).encode()))
+            return _check_in(self._module, L.pcxb_call_double(self._h, n, a))
+        return _check_in(self._module, L.pcxb_call_string(self._h, n, str(a).encode()))
 
     def calls(self):
         """{name: number of arguments} of the calls the block registered"""
-        L = load()
+        L = load(self._module)
         n = C.c_size_t()
-        _check(L.pcxb_call_count(self._h, C.byref(n)))
+        _check_in(self._module, L.pcxb_call_count(self._h, C.byref(n)))
         out = {}
         buf = C.create_string_buffer(128)
         for i in range(n.value):
-            _check(L.pcxb_call_name(self._h, i, buf, len(buf)))
+            _check_in(self._module, L.pcxb_call_name(self._h, i, buf, len(buf)))
             out[buf.value.decode()] = int(L.pcxb_call_arity(self._h, buf.value))
         return out
 
     def activate(self):
-        _check(load().pcxb_activate(self._h))
+        _check_in(self._module, load(self._module).pcxb_activate(self._h))
 
     def deactivate(self):
-        _check(load().pcxb_deactivate(self._h))
+        _check_in(self._module, load(self._module).pcxb_deactivate(self._h))
 
     def connect_signal(self, signal, dst, slot):
         """Topology::connect(self, signal, dst, slot): later emissions call dst's registered `slot` synchronously."""
-        _check(load().pcxb_connect_signal(self._h, signal.encode(), dst._h, slot.encode()))
+        _check_in(self._module, load(self._module).pcxb_connect_signal(self._h, signal.encode(), dst._h, slot.encode()))
         self._slots.append(dst)
 
     def buffer_manager(self, is_output):
         name = C.create_string_buffer(64)
         sz = C.c_size_t()
-        _check(load().pcxb_buffer_manager(self._h, int(is_output), name, 64, C.byref(sz)))
+        _check_in(self._module, load(self._module).pcxb_buffer_manager(self._h, int(is_output), name, 64, C.byref(sz)))
         return name.value.decode(), sz.value
 
     def port_buffer(self, is_output, shape, dtype):
@@ -266,7 +291,7 @@ class Block:
         array of `shape` / `dtype` over the slab -- page-locked for the device-backed blocks.  Returns (array, pinned)."""
         nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p, sz, pin = C.c_void_p(), C.c_size_t(), C.c_int()
-        _check(load().pcxb_acquire_buffer(self._h, int(is_output), nbytes, C.byref(p), C.byref(sz), C.byref(pin)))
+        _check_in(self._module, load(self._module).pcxb_acquire_buffer(self._h, int(is_output), nbytes, C.byref(p), C.byref(sz), C.byref(pin)))
         arr = np.ctypeslib.as_array((C.c_char * nbytes).from_address(p.value)).view(dtype).reshape(shape)
         return arr, bool(pin.value)
 
@@ -274,7 +299,7 @@ class Block:
         """The buffer a scheduler would plant on the edge self.output(0) -> downstream.input(0) (pcxb_link_buffer).
         Returns (address, kind): kind 2 = device memory (two blocks of this module), 1 = page-locked host, 0 = pageable."""
         p, sz, kind = C.c_void_p(), C.c_size_t(), C.c_int()
-        _check(load().pcxb_link_buffer(self._h, downstream._h, nbytes, C.byref(p), C.byref(sz), C.byref(kind)))
+        _check_in(self._module, load(self._module).pcxb_link_buffer(self._h, downstream._h, nbytes, C.byref(p), C.byref(sz), C.byref(kind)))
         return p.value, kind.value
 
     def work_raw(self, in_ptr, in_elems, out_ptr, out_elems, labels=()):
@@ -283,7 +308,7 @@ class Block:
         for i, l in enumerate(labels):
             l._to_c(labs[i])
         c, p, r, npost = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
-        _check(load().pcxb_work(self._h, C.c_void_p(in_ptr), in_elems, labs, len(labels), C.c_void_p(out_ptr), out_elems, C.byref(c), C.byref(p),
+        _check_in(self._module, load(self._module).pcxb_work(self._h, C.c_void_p(in_ptr), in_elems, labs, len(labels), C.c_void_p(out_ptr), out_elems, C.byref(c), C.byref(p),
                                 C.byref(r), posted, 64, C.byref(npost)))
         return c.value, p.value, (None if r.value == _SIZE_MAX else r.value)
 
@@ -291,24 +316,24 @@ class Block:
         """pcxb_work_loop: `reps` work() calls on the same buffers from native code.  Returns (seconds, consumed, produced) of the loop /
         its last call."""
         t, c, p = C.c_double(), C.c_size_t(), C.c_size_t()
-        _check(load().pcxb_work_loop(self._h, C.c_void_p(in_ptr), in_elems, C.c_void_p(out_ptr), out_elems, reps, C.byref(t), C.byref(c), C.byref(p)))
+        _check_in(self._module, load(self._module).pcxb_work_loop(self._h, C.c_void_p(in_ptr), in_elems, C.c_void_p(out_ptr), out_elems, reps, C.byref(t), C.byref(c), C.byref(p)))
         return t.value, c.value, p.value
 
     def initial_reserve(self):
         r = C.c_size_t()
-        load().pcxb_initial_reserve(self._h, C.byref(r))
+        load(self._module).pcxb_initial_reserve(self._h, C.byref(r))
         return None if r.value == _SIZE_MAX else r.value
 
     def ports(self, is_output):
         """[(name, dtype name, dimension, bytes per element, preloaded elements)] -- indexed ports first."""
-        L = load()
+        L = load(self._module)
         cnt = C.c_size_t()
-        _check(L.pcxb_num_ports(self._h, int(is_output), C.byref(cnt)))
+        _check_in(self._module, L.pcxb_num_ports(self._h, int(is_output), C.byref(cnt)))
         out = []
         for k in range(cnt.value):
             nm, dt = C.create_string_buffer(64), C.create_string_buffer(64)
             dim, nb, pre = C.c_size_t(), C.c_size_t(), C.c_size_t()
-            _check(L.pcxb_port_info(self._h, int(is_output), k, nm, 64, dt, 64, C.byref(dim), C.byref(nb), C.byref(pre)))
+            _check_in(self._module, L.pcxb_port_info(self._h, int(is_output), k, nm, 64, dt, 64, C.byref(dim), C.byref(nb), C.byref(pre)))
             out.append((nm.value.decode(), dt.value.decode(), dim.value, nb.value, pre.value))
         return out
 
@@ -316,7 +341,7 @@ class Block:
         """One work() call with a buffer planted on every port (ins: one array per input port, out_elems:
         room per output port).  inline=True plants input 0's buffer as output 0 (the buffer forwarding the
         reference's setReadBeforeWrite enables).  Returns (outs trimmed to produced, consumed, produced)."""
-        L = load()
+        L = load(self._module)
         ip, op = self.ports(0), self.ports(1)
         xs = [np.ascontiguousarray(as_pairs(x)) for x in ins]
         if isinstance(out_elems, int):
@@ -332,7 +357,7 @@ class Block:
         out_ptrs = (C.c_void_p * len(ys))(*[y.ctypes.data for y in ys])
         out_n = (C.c_size_t * len(ys))(*[int(n) for n in out_elems])
         cons, prod = (C.c_size_t * len(xs))(), (C.c_size_t * len(ys))()
-        _check(L.pcxb_work_ports(self._h, len(xs), in_ptrs, in_n, len(ys), out_ptrs, out_n, cons, prod))
+        _check_in(self._module, L.pcxb_work_ports(self._h, len(xs), in_ptrs, in_n, len(ys), out_ptrs, out_n, cons, prod))
         produced = [int(v) for v in prod]
         return [y[:p * port[2]] for y, p, port in zip(ys, produced, op)], [int(v) for v in cons], produced
 
@@ -353,7 +378,7 @@ class Block:
             l._to_c(labs[i])
         posted = (PcxbLabel * 64)()
         c, p, r, npost = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
-        _check(load().pcxb_work(self._h, x.ctypes.data_as(C.c_void_p), in_elems, labs, len(labels),
+        _check_in(self._module, load(self._module).pcxb_work(self._h, x.ctypes.data_as(C.c_void_p), in_elems, labs, len(labels),
                                 y.ctypes.data_as(C.c_void_p), out_elems, C.byref(c), C.byref(p), C.byref(r),
                                 posted, 64, C.byref(npost)))
         reserve = None if r.value == _SIZE_MAX else r.value
@@ -387,6 +412,6 @@ class CircularBuffer:
             pass
 
 
-def make(path, dtype=None, *args, dimension=1):
-    """BlockRegistry::make(path, dtype, *args)."""
-    return Block(path, dtype, *args, dimension=dimension)
+def make(path, dtype=None, *args, dimension=1, module="comms"):
+    """BlockRegistry::make(path, dtype, *args) in the registry of `module` (MODULES)."""
+    return Block(path, dtype, *args, dimension=dimension, module=module)

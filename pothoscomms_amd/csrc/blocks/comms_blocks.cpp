@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "pcx.h"
+#include "pcx_block_util.hpp"
 #include "pcx_framework.hpp"
 
 using pcxfw::Block;
@@ -41,21 +42,8 @@ using pcxfw::Label;
 
 namespace {
 
-// DType element name -> (pcx_scalar, complex?)
-bool parseElemType(const DType &dt, int &scalar, bool &cplx)
-{
-    std::string n = DType::fromDType(dt, 1).name();
-    cplx = n.compare(0, 8, "complex_") == 0;
-    if (cplx) n = n.substr(8);
-    if (n == "float64") scalar = PCX_F64;
-    else if (n == "float32") scalar = PCX_F32;
-    else if (n == "int64") scalar = PCX_I64;
-    else if (n == "int32") scalar = PCX_I32;
-    else if (n == "int16") scalar = PCX_I16;
-    else if (n == "int8") scalar = PCX_I8;
-    else return false;
-    return true;
-}
+using namespace pcxblk;     // parseElemType, check, OnDevice, kDomain, the port-slab bounds (pcx_block_util.hpp)
+
 // the arithmetic factory also takes the unsigned types (Arithmetic.cpp:288-291)
 bool parseArithType(const DType &dt, int &scalar, bool &cplx)
 {
@@ -78,14 +66,6 @@ DType realOf(const DType &dt)
     std::string n = DType::fromDType(dt, 1).name();
     if (n.compare(0, 8, "complex_") == 0) n = n.substr(8);
     return DType(n, dt.dimension());
-}
-// ABI status -> the exception type the reference would throw at that point
-void check(int rc, const std::string &where)
-{
-    if (rc == PCX_OK) return;
-    const std::string msg = pcx_last_error();
-    if (rc == PCX_ERR_ARG) throw InvalidArgumentException(where, msg);
-    throw pcxfw::Exception(where, msg);
 }
 
 // EXTENSION (not in the reference) of the integer FIR / Rotate / Scale blocks: setQFormat("HALF_Q,TRUNCATE,FLOOR") names the reading of
@@ -143,7 +123,6 @@ struct BlockQFormat {
  * block: slab size x the framework's buffers per port (4 by default) x the ports that bring their own manager.
  **********************************************************************/
 constexpr size_t kPortSlabBytes = 64u << 20;
-constexpr size_t kPortSlabMin = 64u << 10, kPortSlabMax = 1u << 30;
 #ifdef PCX_WITH_POTHOS
 // Pothos build: a pool of page-locked slabs behind Pothos::BufferManager's PUBLIC interface (init / empty / pop / push over
 // setFrontBuffer) -- the pool logic of the framework's own "generic" manager, which lives in PothosCore's library
@@ -227,27 +206,7 @@ static pcxfw::BufferManager::Sptr deviceManager(const std::string &name, size_t 
 // block connected to the same output reads the bytes -- and nothing short of changing PothosCore can tell those "this is device
 // memory".  An unchanged three-block chain therefore pays PCIe per edge inside Pothos (1.1-1.6 Gsamples/s against 3.8-5.7 for the
 // fused /comms/fm_demod_chain block, tools/chain_path.py): the fused block is the remedy, not device pointers in
-// the framework's hands.
-static const char *const kDomain = "pcx-hip";
-
-// the calling thread's current device for the length of a scope (the C ABI binds a handle to the device current when it is
-// CREATED and runs the stateless maps on the device current when they are CALLED, include/pcx.h)
-class OnDevice {
-public:
-    explicit OnDevice(int device, const char *where = "DeviceBlock") : _prev(-1)
-    {
-        int cur = -1;
-        if (device < 0 || pcx_get_device(&cur) != PCX_OK || cur == device) return;
-        check(pcx_set_device(device), where);
-        _prev = cur;
-    }
-    ~OnDevice() { if (_prev >= 0) (void)pcx_set_device(_prev); }
-    OnDevice(const OnDevice &) = delete;
-    OnDevice &operator=(const OnDevice &) = delete;
-
-private:
-    int _prev;
-};
+// the framework's hands.  (kDomain: pcx_block_util.hpp)
 
 /***********************************************************************
  * What every block of this module has on top of its reference counterpart: the GPU it lives on and the size of its port slabs.

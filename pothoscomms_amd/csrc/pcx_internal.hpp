@@ -218,6 +218,23 @@ int launch_angle(int scalar, const void *in, void *out, size_t n, hipStream_t st
 int launch_arith(int scalar, int is_complex, int op, const void *in0, const void *in1, void *out, size_t n, hipStream_t st);
 int launch_split_complex(int scalar, const void *in, void *re, void *im, size_t n, hipStream_t st);
 int launch_combine_complex(int scalar, const void *re, const void *im, void *out, size_t n, hipStream_t st);
+// (dc_removal.hip) /comms/dc_removal: the shape of a configured handle and its two paths
+struct DcrShape {
+    int scalar = PCX_F32;
+    bool cplx = false;
+    int64_t D = 0;          // average size
+    int C = 0;              // cascade size
+    int64_t H = 0;          // fused path: input samples carried across calls (C * (D-1), C * D for real int8)
+    int64_t dacc = 0;       // D narrowed to the accumulator type
+    int64_t nrm = 0;        // complex integers: dacc * dacc narrowed to the accumulator type
+};
+bool dcr_telescopes(int scalar, bool cplx);
+int64_t dcr_fused_halo_max();
+size_t dcr_tile();
+int launch_dcr_fused(const DcrShape &p, const void *in, void *out, size_t n, const void *hx, hipStream_t st);
+int launch_dcr_stage(const DcrShape &p, const void *u, size_t m, const void *hist, void *tsum, void *b1, void *y, const void *x,
+                     const void *hist0, bool last, hipStream_t st);
+int launch_dcr_shift(void *state, const void *u, size_t m_bytes, size_t len_bytes, void *tmp, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

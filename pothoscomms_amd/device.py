@@ -253,6 +253,49 @@ class FreqDemod(_Handle):
         _lib.check(_lib.load().pcx_freqdemod_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
 
 
+class DCRemoval(_Handle):
+    """pcx_dcremoval_*: filter/DCRemoval.cpp's cascaded moving-average DC blocker, history and accumulators carried on the device.
+
+    Integer types give the reference's bits (wrap-around included); float types are computed in exact arithmetic."""
+    _destroy = "pcx_dcremoval_destroy"
+
+    def __init__(self, dtype="complex_float32", average_size=512, cascade_size=2):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, self.cplx = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_dcremoval_create(self.scalar, int(self.cplx), C.byref(self._h)))
+        if (average_size, cascade_size) != (512, 2):
+            self.set_sizes(average_size, cascade_size)
+
+    def set_sizes(self, average_size, cascade_size):
+        _lib.check(_lib.load().pcx_dcremoval_set_sizes(self._h, int(average_size), int(cascade_size)))
+
+    def sizes(self):
+        d, c = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.load().pcx_dcremoval_get_sizes(self._h, C.byref(d), C.byref(c)))
+        return d.value, c.value
+
+    def reset(self):
+        _lib.check(_lib.load().pcx_dcremoval_reset(self._h))
+
+    def process(self, x, out=None):
+        """x: (n,) real or (n, 2) complex pairs (or a complex numpy array) of the element type"""
+        x = as_pairs(x) if self.cplx else np.ascontiguousarray(x)
+        if x.dtype != NP_SCALAR[self.scalar]:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "dc_removal: %s input for a %s block" % (x.dtype, self.dtype))
+        if out is None:
+            y = np.zeros_like(x)
+        else:
+            y = out
+            if not (isinstance(y, np.ndarray) and y.dtype == x.dtype and y.shape == x.shape and y.flags.c_contiguous):
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "dc_removal: out must be a contiguous %s array of shape %s" % (x.dtype, x.shape))
+        _lib.check(_lib.load().pcx_dcremoval_process(self._h, _np_ptr(x), _np_ptr(y), x.shape[0]))
+        return y
+
+    def process_dev(self, x, y, n, stream=None):
+        _lib.check(_lib.load().pcx_dcremoval_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
