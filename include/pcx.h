@@ -328,6 +328,38 @@ PCX_API int pcx_dcremoval_process(pcx_dcremoval *h, const void *in, void *out, s
 PCX_API int pcx_dcremoval_process_dev(pcx_dcremoval *h, const void *in_dev, void *out_dev, size_t n, void *stream);
 
 /* ===================================================================== *
+ *  /comms/envelope_detector      filter/EnvelopeDetector.cpp
+ * ===================================================================== */
+typedef struct pcx_envelope pcx_envelope;
+/* EnvelopeDetectorFactory(dtype), EnvelopeDetector.cpp:163-178: scalar in {F64, F32, I64, I32, I16, I8}, real or complex; the
+ * output is float32 whatever the input.  Created as the reference constructs the block: every gain 0 (a handle whose setters were
+ * never called outputs zeros), envelope 0, lookahead 0.  The device state and workspace are allocated here. */
+PCX_API int pcx_envelope_create(int scalar, int is_complex, pcx_envelope **out);
+PCX_API int pcx_envelope_destroy(pcx_envelope *h);
+/* setAttack / setRelease (EnvelopeDetector.cpp:76-99): gain = std::exp(-1/t) and 1 - gain in float, on the host.  Neither resets
+ * the envelope. */
+PCX_API int pcx_envelope_set_attack(pcx_envelope *h, float attack);
+PCX_API int pcx_envelope_get_attack(const pcx_envelope *h, float *attack);
+PCX_API int pcx_envelope_set_release(pcx_envelope *h, float release);
+PCX_API int pcx_envelope_get_release(const pcx_envelope *h, float *release);
+PCX_API int pcx_envelope_set_lookahead(pcx_envelope *h, size_t lookahead);
+PCX_API int pcx_envelope_get_lookahead(const pcx_envelope *h, size_t *lookahead);
+/* the envelope back to 0 (for API users: the block never calls it, as the reference has no activate()) */
+PCX_API int pcx_envelope_reset(pcx_envelope *h);
+/* the carried envelope after the handle's last call (waits for that call) */
+PCX_API int pcx_envelope_get_state(pcx_envelope *h, float *envelope);
+/* work()'s loop (EnvelopeDetector.cpp:110-148) for n outputs: reads n + lookahead input elements from in, out[i] from in[i +
+ * lookahead], writes n floats, carries the envelope.  Bit for bit the reference's float32 arithmetic (any NaN for a NaN).
+ * process_dev synchronises nothing and allocates nothing: it can be captured into a graph. */
+PCX_API int pcx_envelope_process(pcx_envelope *h, const void *in, void *out, size_t n);
+PCX_API int pcx_envelope_process_dev(pcx_envelope *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+/* the last call's path counts (waits for that call): chunks computed speculatively, chunks whose repair pass rewrote outputs,
+ * chunks the in-order resolve pass re-ran.  Slow time constants show up as repaired and resolved chunks. */
+PCX_API int pcx_envelope_get_stats(pcx_envelope *h, uint64_t *chunks, uint64_t *repaired, uint64_t *resolved);
+/* tuning: warm-up samples in front of each speculative chunk; 0 (the default) derives it from the gains */
+PCX_API int pcx_envelope_set_warmup(pcx_envelope *h, size_t warmup);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

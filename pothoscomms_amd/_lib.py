@@ -114,6 +114,20 @@ SIGNATURES = {
     "pcx_dcremoval_reset": (_i, [_vp]),
     "pcx_dcremoval_process": (_i, [_vp, _vp, _vp, _sz]),
     "pcx_dcremoval_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_envelope_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "pcx_envelope_destroy": (_i, [_vp]),
+    "pcx_envelope_set_attack": (_i, [_vp, C.c_float]),
+    "pcx_envelope_get_attack": (_i, [_vp, C.POINTER(C.c_float)]),
+    "pcx_envelope_set_release": (_i, [_vp, C.c_float]),
+    "pcx_envelope_get_release": (_i, [_vp, C.POINTER(C.c_float)]),
+    "pcx_envelope_set_lookahead": (_i, [_vp, _sz]),
+    "pcx_envelope_get_lookahead": (_i, [_vp, _psz]),
+    "pcx_envelope_reset": (_i, [_vp]),
+    "pcx_envelope_get_state": (_i, [_vp, C.POINTER(C.c_float)]),
+    "pcx_envelope_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_envelope_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_envelope_get_stats": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pcx_envelope_set_warmup": (_i, [_vp, _sz]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

@@ -28,8 +28,9 @@ class PcxbLabel(C.Structure):
 
 _blib = None
 # the module libraries: "comms" is libpcx_blocks.so (comms_blocks.cpp, fir_designer.cpp), "filter" libpcx_filter_blocks.so
-# (filter_blocks.cpp: /comms/dc_removal) -- one registry each, as Pothos loads one module library per source directory
-MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so")}
+# (filter_blocks.cpp: /comms/dc_removal), "envelope" libpcx_envelope_blocks.so (envelope_blocks.cpp: /comms/envelope_detector) -- one registry each, as Pothos loads one module library per source directory
+MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
+           "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so")}
 _mlibs = {}
 
 
@@ -232,7 +233,7 @@ class Block:
             return [int(v[k]) for k in range(cnt.value)]
         if not args:   # getter
             if name in ("getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
-                        "getAverageSize", "getCascadeSize"):
+                        "getAverageSize", "getCascadeSize", "getLookahead"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value
@@ -241,7 +242,7 @@ class Block:
                 _check_in(self._module, L.pcxb_get_bool(self._h, n, C.byref(v)))
                 return bool(v.value)
             if name in ("getPhase", "getFactor", "sampleRate", "frequencyLower", "frequencyUpper", "bandwidthTrans", "alpha",
-                        "stopDB", "passDB", "gain"):
+                        "stopDB", "passDB", "gain", "getAttack", "getRelease"):
                 v = C.c_double()
                 _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
                 return v.value

@@ -235,6 +235,20 @@ int launch_dcr_fused(const DcrShape &p, const void *in, void *out, size_t n, con
 int launch_dcr_stage(const DcrShape &p, const void *u, size_t m, const void *hist, void *tsum, void *b1, void *y, const void *x,
                      const void *hist0, bool last, hipStream_t st);
 int launch_dcr_shift(void *state, const void *u, size_t m_bytes, size_t len_bytes, void *tmp, hipStream_t st);
+// (envelope.hip) /comms/envelope_detector: the gains of a configured handle and how a call slice is cut
+struct EnvGains {
+    float gA = 0, oA = 0, gR = 0, oR = 0;     // attack / release gain and one minus it (EnvelopeDetector.cpp:76-99)
+};
+struct EnvShape {
+    int scalar = PCX_F32;
+    bool cplx = false;
+    EnvGains g;
+    int64_t C = 256;        // samples per chunk
+    int64_t W = 0;          // warm-up samples in front of a chunk
+};
+// one slice of n outputs (in: the element that feeds out[0]); state: the carried envelope, in and out
+int launch_envelope_slice(const EnvShape &p, const void *in, float *out, size_t n, float *state, float *ends, unsigned char *miss,
+                          unsigned long long *cnt, bool first, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

@@ -296,6 +296,91 @@ class DCRemoval(_Handle):
         _lib.check(_lib.load().pcx_dcremoval_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
 
 
+class EnvelopeDetector(_Handle):
+    """pcx_envelope_*: filter/EnvelopeDetector.cpp's attack/release envelope, float32 out, bit for bit the reference's loop.
+
+    Created as the reference constructs the block (all gains 0, lookahead 0); `attack` / `release` / `lookahead` given here are
+    set through the setters.  process / process_dev take n + lookahead input elements for n outputs."""
+    _destroy = "pcx_envelope_destroy"
+
+    def __init__(self, dtype="complex_float32", attack=None, release=None, lookahead=0):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, self.cplx = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_envelope_create(self.scalar, int(self.cplx), C.byref(self._h)))
+        if attack is not None:
+            self.set_attack(attack)
+        if release is not None:
+            self.set_release(release)
+        if lookahead:
+            self.set_lookahead(lookahead)
+
+    def set_attack(self, attack):
+        _lib.check(_lib.load().pcx_envelope_set_attack(self._h, float(attack)))
+
+    def attack(self):
+        v = C.c_float()
+        _lib.check(_lib.load().pcx_envelope_get_attack(self._h, C.byref(v)))
+        return v.value
+
+    def set_release(self, release):
+        _lib.check(_lib.load().pcx_envelope_set_release(self._h, float(release)))
+
+    def release(self):
+        v = C.c_float()
+        _lib.check(_lib.load().pcx_envelope_get_release(self._h, C.byref(v)))
+        return v.value
+
+    def set_lookahead(self, lookahead):
+        _lib.check(_lib.load().pcx_envelope_set_lookahead(self._h, int(lookahead)))
+
+    def lookahead(self):
+        v = C.c_size_t()
+        _lib.check(_lib.load().pcx_envelope_get_lookahead(self._h, C.byref(v)))
+        return v.value
+
+    def set_warmup(self, warmup):
+        """warm-up samples in front of each speculative chunk (0: derived from the gains)"""
+        _lib.check(_lib.load().pcx_envelope_set_warmup(self._h, int(warmup)))
+
+    def reset(self):
+        _lib.check(_lib.load().pcx_envelope_reset(self._h))
+
+    def state(self):
+        v = C.c_float()
+        _lib.check(_lib.load().pcx_envelope_get_state(self._h, C.byref(v)))
+        return v.value
+
+    def stats(self):
+        """(chunks, repaired, resolved) of the last call"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _lib.check(_lib.load().pcx_envelope_get_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def process(self, x, n=None, out=None):
+        """x: (m,) real or (m, 2) complex pairs (or a complex numpy array) of the element type; n outputs (default m - lookahead)
+        from x[0 : n + lookahead]"""
+        x = as_pairs(x) if self.cplx else np.ascontiguousarray(x)
+        if x.dtype != NP_SCALAR[self.scalar] or x.ndim != (2 if self.cplx else 1):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "envelope_detector: %s%s input for a %s block" % (x.dtype, x.shape, self.dtype))
+        L = self.lookahead()
+        if n is None:
+            n = max(0, x.shape[0] - L)
+        if n + L > x.shape[0]:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "envelope_detector: %d outputs need %d input elements, %d given" % (n, n + L, x.shape[0]))
+        if out is None:
+            y = np.zeros(n, np.float32)
+        else:
+            y = out
+            if not (isinstance(y, np.ndarray) and y.dtype == np.float32 and y.shape == (n,) and y.flags.c_contiguous):
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "envelope_detector: out must be a contiguous float32 array of shape (%d,)" % n)
+        _lib.check(_lib.load().pcx_envelope_process(self._h, _np_ptr(x), _np_ptr(y), n))
+        return y
+
+    def process_dev(self, x, y, n, stream=None):
+        _lib.check(_lib.load().pcx_envelope_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
