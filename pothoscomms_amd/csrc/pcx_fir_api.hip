@@ -151,6 +151,8 @@ static int fir_sync_tables(pcx_fir *h)
     case PCX_I8: PCX_TRY(fir_upload_rows<int16_t>(h, true)); break;
     }
     h->have_ols = false;
+    h->ols_parts = 0;     // set below by the plans that use them: none may see the value of an earlier configuration
+    h->ols_log2n = 0;
     if (!h->sched.p) {
         PCX_TRY(h->sched.ensure_zeroed(kSchedBytes));
     }
@@ -598,8 +600,8 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
     if (gate_word) {
         // a gated call: only the plain complex_float32 M = L = 1 plan on 4096-sample blocks has the gate (and only its dealt launch,
         // launch_fir_cf32_ols4096 decides).  Anything else: *gated stays 0, nothing has been queued, the caller orders the halo itself.
-        const bool plain = algo == PCX_FIR_OLS_FFT && !h->have_interp_real && !h->have_interp64 && !h->have_ols_real64 && !h->have_ols64 &&
-                           !h->have_ols_int && !h->have_real_ols && !h->have_interp && !h->have_decim && !h->have_poly && h->ols_parts == 0;
+        // (The one plan that is accepted is named, rather than the others excluded: a plan added later has no gate until it says so.)
+        const bool plain = algo == PCX_FIR_OLS_FFT && fir_fast_applicable(h) && h->have_ols && h->ols_parts == 0;
         if (!plain) return PCX_OK;
         rc = launch_fir_cf32_ols4096(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->tw4096.p, h->sched.p, st, gate_word, gate_value, gated, h->slots);
         if (rc != PCX_OK || !*gated) return rc;

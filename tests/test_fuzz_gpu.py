@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.util import TOL, ang_err, d2h, diff_note, h2d, nerr, rand_stream
+from tests.util import TOL, ang_err, bands_intact, d2h, diff_note, guarded, h2d, nerr, rand_stream
 
 pytestmark = pytest.mark.gpu
 SEEDS = range(int(os.environ.get("PCX_FUZZ_SEEDS", "12")))
@@ -353,22 +353,7 @@ def test_fft_and_demod_blocks_random_chunks(oracle, seed):
 
 
 # ---- guard bands: nothing outside [out, out + produced) may be written, nothing outside the declared input read ----
-GUARD = 4096   # elements of poison on either side
 GSEEDS = range(2 * len(SEEDS))
-
-
-def _guarded(torch, d, n_elems, width, dtype, fill):
-    """A device buffer with GUARD poisoned elements on either side of an n_elems window; returns (whole, window)."""
-    whole = torch.full(((n_elems + 2 * GUARD) * width,), fill, dtype=dtype, device=d)
-    win = whole[GUARD * width:(GUARD + n_elems) * width]
-    return whole, (win.view(-1, width) if width > 1 else win)
-
-
-def _bands_intact(whole, n_elems, width, fill):
-    lo, hi = whole[:GUARD * width], whole[(GUARD + n_elems) * width:]
-    if fill != fill:      # NaN poison
-        return bool(lo.isnan().all()) and bool(hi.isnan().all())
-    return bool((lo == fill).all()) and bool((hi == fill).all())
 
 
 @pytest.mark.parametrize("seed", GSEEDS)
@@ -391,14 +376,14 @@ def test_fir_writes_only_its_outputs_and_reads_only_its_inputs(oracle, dev, seed
     K = f.K
     n_iter = int(rng.integers(1, 40000)) // M * M + M
     n_in, n_out = n_iter + K - 1, n_iter // M * L
-    xw, x = _guarded(torch, d, n_in, 2, torch.float32, nan)
-    yw, y = _guarded(torch, d, n_out, 2, torch.float32, nan)
+    xw, x = guarded(torch, d, n_in, 2, torch.float32, nan)
+    yw, y = guarded(torch, d, n_out, 2, torch.float32, nan)
     xh = rng.uniform(-1, 1, (n_in, 2)).astype(np.float32)
     x.copy_(torch.from_numpy(xh).to(d))
     c, p = f.process_dev(x, y, n_in, n_out)
     torch.cuda.synchronize()
     assert (c, p) == (n_iter, n_out)
-    assert _bands_intact(yw, n_out, 2, nan), (L, M, ntaps, algo)
+    assert bands_intact(yw, n_out, 2, nan), (L, M, ntaps, algo)
     got = y.cpu().numpy()
     assert np.isfinite(got).all(), (L, M, ntaps, algo)        # no NaN from beyond the input window
     blk = oracle.Fir(oracle.F32, True, True)
@@ -425,15 +410,15 @@ def test_real_fir_writes_only_its_outputs_and_reads_only_its_inputs(oracle, dev,
     f.set_taps(h); f.set_decimation(M)
     n_out = int(rng.choice([1, 2, 31, 33, 2047, 2049, int(rng.integers(1, 60000 // M + 2))]))
     n_in = n_out * M + ntaps - 1
-    xw, x = _guarded(torch, d, n_in, 1, torch.float32, nan)
-    yw, y = _guarded(torch, d, n_out, 1, torch.float32, nan)
+    xw, x = guarded(torch, d, n_in, 1, torch.float32, nan)
+    yw, y = guarded(torch, d, n_out, 1, torch.float32, nan)
     xh = rng.uniform(-1, 1, n_in).astype(np.float32)
     x.copy_(torch.from_numpy(xh).to(d))
     c, p = f.process_dev(x, y, n_in, n_out)
     torch.cuda.synchronize()
     assert (c, p) == (n_out * M, n_out)
     assert f.last_algo == _lib.FIR_OLS_FFT or (M > 1 and ntaps < 16)
-    assert _bands_intact(yw, n_out, 1, nan), (ntaps, n_out, M)
+    assert bands_intact(yw, n_out, 1, nan), (ntaps, n_out, M)
     got = y.cpu().numpy()
     assert np.isfinite(got).all(), (ntaps, n_out)             # no NaN from beyond the input window
     blk = oracle.Fir(oracle.F32, False, False)
@@ -454,14 +439,14 @@ def test_fft_writes_only_its_frames(oracle, dev, seed):
                      ("complex_int16", torch.int16, oracle.I16)][seed % 3]
     nframes = int(rng.integers(1, 9)) if nbins >= 4096 else int(rng.integers(1, 70))
     fill = float("nan") if sc != oracle.I16 else 12345
-    xw, x = _guarded(torch, d, nbins * nframes, 2, td, fill)
-    yw, y = _guarded(torch, d, nbins * nframes, 2, td, fill)
+    xw, x = guarded(torch, d, nbins * nframes, 2, td, fill)
+    yw, y = guarded(torch, d, nbins * nframes, 2, td, fill)
     xh = rand_stream(rng, sc, nbins * nframes, True) if sc != oracle.I16 else rng.integers(-3000, 3000, (nbins * nframes, 2)).astype(np.int16)
     x.copy_(torch.from_numpy(xh).to(d))
     inv = bool(seed & 1)
     dev.Fft(dtype, nbins, inv).transform_dev(x, y, nframes)
     torch.cuda.synchronize()
-    assert _bands_intact(yw, nbins * nframes, 2, fill), (nbins, dtype)
+    assert bands_intact(yw, nbins * nframes, 2, fill), (nbins, dtype)
     got, ref = y.cpu().numpy(), oracle.fft(xh, nbins, inv)
     if sc == oracle.I16:
         assert np.array_equal(got, ref)
@@ -480,8 +465,8 @@ def test_fm_chain_writes_only_its_outputs(oracle, dev, seed):
     n = int(rng.integers(1, 50000))
     h = rng.normal(size=ntaps) / ntaps
     nan = float("nan")
-    xw, x = _guarded(torch, d, n + ntaps - 1, 2, torch.float32, nan)
-    yw, y = _guarded(torch, d, n, 1, torch.float32, nan)
+    xw, x = guarded(torch, d, n + ntaps - 1, 2, torch.float32, nan)
+    yw, y = guarded(torch, d, n, 1, torch.float32, nan)
     ph = np.cumsum(rng.uniform(-0.5, 0.5, n + ntaps - 1))
     xh = np.stack([np.cos(ph), np.sin(ph)], 1).astype(np.float32)
     x.copy_(torch.from_numpy(xh).to(d))
@@ -489,7 +474,7 @@ def test_fm_chain_writes_only_its_outputs(oracle, dev, seed):
     ch.set_algo([_lib.FIR_AUTO, _lib.FIR_DIRECT, _lib.FIR_OLS_FFT][seed % 3])
     assert ch.process_dev(x, y, n + ntaps - 1, n) == (n, n)
     torch.cuda.synchronize()
-    assert _bands_intact(yw, n, 1, nan), ntaps
+    assert bands_intact(yw, n, 1, nan), ntaps
     got = y.cpu().numpy()
     assert np.isfinite(got).all()
     fir = oracle.Fir(oracle.F32, True, False); fir.set_taps(h); fir.activate()

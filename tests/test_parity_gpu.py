@@ -870,7 +870,8 @@ def test_fir_host_path_large_buffer(oracle, dev):
 @pytest.mark.parametrize("seed", range(int(os.environ.get("PCX_FUZZ_SEEDS", "24"))))
 def test_fir_randomised_configurations(oracle, dev, seed):
     """random (type, taps kind, K, L, M, buffer sizes, output room) through AUTO vs the oracle's work();
-    PCX_FUZZ_SEEDS=N widens the sweep (soak runs)"""
+    PCX_FUZZ_SEEDS=N widens the sweep (soak runs).  int64 and the long-tap and many-row branches below come in only from
+    seed 24, beyond the default sweep: tests/test_fir_plans_gpu.py reaches those plans (and every other) row by row."""
     rng = np.random.default_rng(1000 + seed)
     scalar = [oracle.F32, oracle.F32, oracle.F32, oracle.F64, oracle.I16, oracle.I8, oracle.I32, oracle.I64][seed % 8 if seed >= 24 else seed % 7]
     is_complex = bool(rng.integers(0, 4) > 0) or scalar != oracle.F32

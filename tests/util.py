@@ -6,6 +6,7 @@ from oracle import oracle as o
 SCALARS = [o.F64, o.F32, o.I64, o.I32, o.I16, o.I8]
 NAMES = {o.F64: "float64", o.F32: "float32", o.I64: "int64", o.I32: "int32", o.I16: "int16", o.I8: "int8"}
 TOL = 1e-5  # north_star: within 1e-5 relative for float32, normalised by max|ref|
+GUARD = 4096   # elements of poison on either side of a guarded device window
 
 
 def rand_stream(rng, scalar, n, is_complex, amp=None):
@@ -72,3 +73,19 @@ def d2h(t):
     out.copy_(t)
     torch.cuda.current_stream(t.device).synchronize()
     return out.numpy().copy()
+
+
+def guarded(torch, d, n_elems, width, dtype, fill, offset=0):
+    """A device buffer with GUARD + offset poisoned elements in front of an n_elems window and GUARD behind it; returns
+    (whole, window).  An element offset of 1 or 3 leaves the window off the 16-byte alignment of every element narrower than that."""
+    whole = torch.full(((n_elems + 2 * GUARD + offset) * width,), fill, dtype=dtype, device=d)
+    win = whole[(GUARD + offset) * width:(GUARD + offset + n_elems) * width]
+    return whole, (win.view(-1, width) if width > 1 else win)
+
+
+def bands_intact(whole, n_elems, width, fill, offset=0):
+    """the poison of guarded() on either side of the window is untouched"""
+    lo, hi = whole[:(GUARD + offset) * width], whole[(GUARD + offset + n_elems) * width:]
+    if fill != fill:      # NaN poison
+        return bool(lo.isnan().all()) and bool(hi.isnan().all())
+    return bool((lo == fill).all()) and bool((hi == fill).all())
