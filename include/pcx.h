@@ -360,6 +360,34 @@ PCX_API int pcx_envelope_get_stats(pcx_envelope *h, uint64_t *chunks, uint64_t *
 PCX_API int pcx_envelope_set_warmup(pcx_envelope *h, size_t warmup);
 
 /* ===================================================================== *
+ *  /comms/iir_filter      filter/IIRFilter.cpp
+ * ===================================================================== */
+typedef struct pcx_iir pcx_iir;
+/* pcx_iir_get_plan: how a configured handle computes */
+enum { PCX_IIR_SCAN = 0, PCX_IIR_SERIAL = 1 };
+/* IIRFilterFactory(dtype), IIRFilter.cpp:107-121: scalar in {F64, F32, I64, I32, I16, I8}, real or complex (two independent real
+ * recurrences).  Created with the reference's default taps [0.0676, 0.135, 0.0676, 1, -1.142, 0.412] and a zero history.  The device
+ * state and workspace are allocated here, for every order and one slice. */
+PCX_API int pcx_iir_create(int scalar, int is_complex, pcx_iir **out);
+PCX_API int pcx_iir_destroy(pcx_iir *h);
+/* setTaps (IIRFilter.cpp:63-69): b[0..N] then a[0..N], 1 <= N + 1 <= 33, normalised by a[0] in double.  PCX_ERR_ARG, checked before
+ * the handle: no taps, an odd count, more than 66, a non-finite tap, a[0] == 0.  Chooses the plan (Schur-Cohn: SCAN for a stable
+ * filter, SERIAL otherwise) and zeroes the history. */
+PCX_API int pcx_iir_set_taps(pcx_iir *h, const double *taps, size_t n);
+/* the taps as last set: *n = their count, at most cap of them copied */
+PCX_API int pcx_iir_get_taps(const pcx_iir *h, double *taps, size_t cap, size_t *n);
+/* activate(): the history back to zero */
+PCX_API int pcx_iir_reset(pcx_iir *h);
+/* the plan, and for SCAN the a-priori bound: every output before narrowing lies within bound * max|x| of the sequential double
+ * recurrence's value (0 for SERIAL, which is that recurrence bit for bit) */
+PCX_API int pcx_iir_get_plan(const pcx_iir *h, int *plan, double *bound);
+/* work()'s loop (IIRFilter.cpp:82-99) over n elements, the history carried across calls: y = sum b_k x[n-k] - sum a_k y[n-k] in
+ * double, narrowed to the stream type (float32 to nearest; integers toward zero, saturated, NaN -> 0).  process_dev synchronises
+ * nothing and allocates nothing: it can be captured into a graph. */
+PCX_API int pcx_iir_process(pcx_iir *h, const void *in, void *out, size_t n);
+PCX_API int pcx_iir_process_dev(pcx_iir *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

@@ -17,6 +17,7 @@ ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV = range(4)
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4
 # pcx_fir_algo
 FIR_AUTO, FIR_DIRECT, FIR_OLS_FFT, FIR_EXACT = 0, 1, 2, 3
+IIR_SCAN, IIR_SERIAL = 0, 1          # pcx_iir_get_plan
 
 
 class PcxError(RuntimeError):
@@ -128,6 +129,14 @@ SIGNATURES = {
     "pcx_envelope_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pcx_envelope_get_stats": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pcx_envelope_set_warmup": (_i, [_vp, _sz]),
+    "pcx_iir_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "pcx_iir_destroy": (_i, [_vp]),
+    "pcx_iir_set_taps": (_i, [_vp, _vp, _sz]),
+    "pcx_iir_get_taps": (_i, [_vp, _vp, _sz, _psz]),
+    "pcx_iir_reset": (_i, [_vp]),
+    "pcx_iir_get_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_d)]),
+    "pcx_iir_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_iir_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

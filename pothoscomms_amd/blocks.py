@@ -28,9 +28,10 @@ class PcxbLabel(C.Structure):
 
 _blib = None
 # the module libraries: "comms" is libpcx_blocks.so (comms_blocks.cpp, fir_designer.cpp), "filter" libpcx_filter_blocks.so
-# (filter_blocks.cpp: /comms/dc_removal), "envelope" libpcx_envelope_blocks.so (envelope_blocks.cpp: /comms/envelope_detector) -- one registry each, as Pothos loads one module library per source directory
+# (filter_blocks.cpp: /comms/dc_removal), "envelope" libpcx_envelope_blocks.so (envelope_blocks.cpp: /comms/envelope_detector), "iir"
+# libpcx_iir_blocks.so (iir_blocks.cpp: /comms/iir_filter) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
-           "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so")}
+           "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so")}
 _mlibs = {}
 
 

@@ -249,6 +249,21 @@ struct EnvShape {
 // one slice of n outputs (in: the element that feeds out[0]); state: the carried envelope, in and out
 int launch_envelope_slice(const EnvShape &p, const void *in, float *out, size_t n, float *state, float *ends, unsigned char *miss,
                           unsigned long long *cnt, bool first, hipStream_t st);
+// (iir.hip) /comms/iir_filter: the plan of a configured handle and one call slice
+struct IirShape {
+    int scalar = PCX_F32;
+    bool cplx = false;
+    int N = 2;              // the order
+    int NB = 2;             // SCAN: the order padded to 2, 4, 8, 16 or 32
+    int plan = PCX_IIR_SCAN;
+};
+size_t iir_slice();         // samples per slice
+size_t iir_tile();          // samples per tile
+int iir_history();          // inputs and outputs carried across calls (the largest order)
+// one slice of m samples; xh / ystate: the carried history, in and out; tab: SCAN tables; coef: SERIAL coefficients; z, tin, ytail:
+// workspace of one slice
+int launch_iir_slice(const IirShape &p, const void *in, void *out, size_t m, void *xh, double *ystate, const double *tab, const double *coef,
+                     double *z, double *tin, double *ytail, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

@@ -381,6 +381,59 @@ class EnvelopeDetector(_Handle):
         _lib.check(_lib.load().pcx_envelope_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
 
 
+class IIRFilter(_Handle):
+    """pcx_iir_*: filter/IIRFilter.cpp's recurrence in double, narrowed to the stream type.
+
+    taps: b[0..N] followed by a[0..N]; None keeps the reference's default.  plan() says how the handle computes: (IIR_SCAN, bound)
+    for a stable filter, every output within bound * max|x| of the sequential recurrence; (IIR_SERIAL, 0.0) otherwise, bit for bit."""
+    _destroy = "pcx_iir_destroy"
+
+    def __init__(self, dtype="complex_float32", taps=None):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, self.cplx = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_iir_create(self.scalar, int(self.cplx), C.byref(self._h)))
+        if taps is not None:
+            self.set_taps(taps)
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+        _lib.check(_lib.load().pcx_iir_set_taps(self._h, _np_ptr(t), t.shape[0]))
+
+    def taps(self):
+        n = C.c_size_t()
+        _lib.check(_lib.load().pcx_iir_get_taps(self._h, None, 0, C.byref(n)))
+        t = np.zeros(n.value, np.float64)
+        _lib.check(_lib.load().pcx_iir_get_taps(self._h, _np_ptr(t), t.shape[0], C.byref(n)))
+        return t
+
+    def reset(self):
+        _lib.check(_lib.load().pcx_iir_reset(self._h))
+
+    def plan(self):
+        """(plan, bound): _lib.IIR_SCAN or _lib.IIR_SERIAL, and the SCAN bound per unit of max|x| (0.0 for SERIAL)"""
+        p, b = C.c_int(), C.c_double()
+        _lib.check(_lib.load().pcx_iir_get_plan(self._h, C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def process(self, x, out=None):
+        """x: (n,) real or (n, 2) complex pairs (or a complex numpy array) of the element type; returns the n outputs in the same layout"""
+        x = as_pairs(x) if self.cplx else np.ascontiguousarray(x)
+        if x.dtype != NP_SCALAR[self.scalar] or x.ndim != (2 if self.cplx else 1) or (self.cplx and x.shape[1] != 2):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "iir_filter: %s%s input for a %s block" % (x.dtype, x.shape, self.dtype))
+        if out is None:
+            y = np.zeros_like(x)
+        else:
+            y = out
+            if not (isinstance(y, np.ndarray) and y.dtype == x.dtype and y.shape == x.shape and y.flags.c_contiguous):
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "iir_filter: out must be a contiguous %s array of shape %s" % (x.dtype, x.shape))
+        _lib.check(_lib.load().pcx_iir_process(self._h, _np_ptr(x), _np_ptr(y), x.shape[0]))
+        return y
+
+    def process_dev(self, x, y, n, stream=None):
+        _lib.check(_lib.load().pcx_iir_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
