@@ -388,6 +388,43 @@ PCX_API int pcx_iir_process(pcx_iir *h, const void *in, void *out, size_t n);
 PCX_API int pcx_iir_process_dev(pcx_iir *h, const void *in_dev, void *out_dev, size_t n, void *stream);
 
 /* ===================================================================== *
+ *  /comms/scrambler, /comms/descrambler      digital/Scrambler.cpp, digital/Descrambler.cpp, digital/lfsr.h
+ *
+ *  One unsigned char per bit in and out; only bit 0 of an input byte counts, an output byte is 0 or 1.  Every output bit and the
+ *  register equal the reference's.
+ * ===================================================================== */
+typedef struct pcx_scrambler pcx_scrambler;
+enum { PCX_SCR_ADDITIVE = 0, PCX_SCR_MULTIPLICATIVE = 1 };
+/* pcx_scrambler_get_plan: how a configured handle computes */
+enum { PCX_SCR_SCAN = 0, PCX_SCR_SERIAL = 1 };
+/* the constructors (Scrambler.cpp:43-62, Descrambler.cpp:43-62): descramble = 0 the scrambler, otherwise the descrambler; multiplicative,
+ * seed 1, setPoly(0x19).  The device state, tables and workspace of one slice are allocated here. */
+PCX_API int pcx_scrambler_create(int descramble, pcx_scrambler **out);
+PCX_API int pcx_scrambler_destroy(pcx_scrambler *h);
+/* setPoly (Scrambler.cpp:64-68): GLFSR_init(poly, seed), lfsr.h:63-83 -- polynomial = poly | 1, data = seed, mask = every bit from the
+ * polynomial's top bit upward (the shift is arithmetic); the mask is KEPT when poly has no bit in 63..1.  Chooses the plan: SCAN when
+ * the polynomial owns the mask's lowest bit m and 0 <= seed < 2^m, SERIAL otherwise. */
+PCX_API int pcx_scrambler_set_poly(pcx_scrambler *h, int64_t poly);
+PCX_API int pcx_scrambler_get_poly(const pcx_scrambler *h, int64_t *poly);
+/* setSeed (Scrambler.cpp:75-79): GLFSR_init(poly, seed) as above */
+PCX_API int pcx_scrambler_set_seed(pcx_scrambler *h, int64_t seed);
+PCX_API int pcx_scrambler_get_seed(const pcx_scrambler *h, int64_t *seed);
+/* setMode (Scrambler.cpp:86-91): PCX_SCR_ADDITIVE or PCX_SCR_MULTIPLICATIVE, anything else PCX_ERR_ARG (checked before the handle);
+ * the register is left alone */
+PCX_API int pcx_scrambler_set_mode(pcx_scrambler *h, int mode);
+PCX_API int pcx_scrambler_get_mode(const pcx_scrambler *h, int *mode);
+PCX_API int pcx_scrambler_get_plan(const pcx_scrambler *h, int *plan);
+/* bits a thread, a tile, a wave of the carry and a slice of the SCAN plan hold (the seams a test wants to straddle) */
+PCX_API int pcx_scrambler_get_geometry(size_t *run, size_t *tile, size_t *group, size_t *slice);
+/* lfsr_t's data and mask after the handle's last call (waits for it) */
+PCX_API int pcx_scrambler_get_state(pcx_scrambler *h, int64_t *data, int64_t *mask);
+/* work()'s loop (Scrambler.cpp:154-181, Descrambler.cpp:154-181) over n bytes, the register carried across calls.  out may be in
+ * itself (in place); any other overlap of the two is PCX_ERR_ARG.  process_dev synchronises nothing and allocates nothing: it can
+ * be captured into a graph. */
+PCX_API int pcx_scrambler_process(pcx_scrambler *h, const void *in, void *out, size_t n);
+PCX_API int pcx_scrambler_process_dev(pcx_scrambler *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

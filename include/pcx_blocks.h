@@ -53,6 +53,7 @@ PCXB_API int pcxb_destroy(pcxb_block *b);
 /* registered calls (registerCall names): one argument of the given kind, or a getter */
 PCXB_API int pcxb_call_double(pcxb_block *b, const char *name, double v);
 PCXB_API int pcxb_call_size(pcxb_block *b, const char *name, size_t v);
+PCXB_API int pcxb_call_int64(pcxb_block *b, const char *name, int64_t v);   /* setPoly, setSeed of /comms/scrambler */
 PCXB_API int pcxb_call_bool(pcxb_block *b, const char *name, int v);
 PCXB_API int pcxb_call_string(pcxb_block *b, const char *name, const char *v);
 PCXB_API int pcxb_call_taps(pcxb_block *b, const char *name, const double *taps, size_t n, int is_complex);
@@ -60,6 +61,7 @@ PCXB_API int pcxb_call_sizes(pcxb_block *b, const char *name, const size_t *v, s
 PCXB_API int pcxb_get_sizes(pcxb_block *b, const char *name, size_t *out, size_t cap, size_t *n);
 PCXB_API int pcxb_get_double(pcxb_block *b, const char *name, double *out);
 PCXB_API int pcxb_get_size(pcxb_block *b, const char *name, size_t *out);
+PCXB_API int pcxb_get_int64(pcxb_block *b, const char *name, int64_t *out);
 PCXB_API int pcxb_get_bool(pcxb_block *b, const char *name, int *out);
 PCXB_API int pcxb_get_string(pcxb_block *b, const char *name, char *out, size_t cap);
 PCXB_API int pcxb_get_taps(pcxb_block *b, const char *name, double *out, size_t cap_doubles, size_t *n, int is_complex);

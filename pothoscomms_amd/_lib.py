@@ -18,6 +18,8 @@ OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4
 # pcx_fir_algo
 FIR_AUTO, FIR_DIRECT, FIR_OLS_FFT, FIR_EXACT = 0, 1, 2, 3
 IIR_SCAN, IIR_SERIAL = 0, 1          # pcx_iir_get_plan
+SCR_ADDITIVE, SCR_MULTIPLICATIVE = 0, 1     # pcx_scrambler_set_mode
+SCR_SCAN, SCR_SERIAL = 0, 1          # pcx_scrambler_get_plan
 
 
 class PcxError(RuntimeError):
@@ -137,6 +139,19 @@ SIGNATURES = {
     "pcx_iir_get_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_d)]),
     "pcx_iir_process": (_i, [_vp, _vp, _vp, _sz]),
     "pcx_iir_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_scrambler_create": (_i, [_i, C.POINTER(_vp)]),
+    "pcx_scrambler_destroy": (_i, [_vp]),
+    "pcx_scrambler_set_poly": (_i, [_vp, C.c_int64]),
+    "pcx_scrambler_get_poly": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "pcx_scrambler_set_seed": (_i, [_vp, C.c_int64]),
+    "pcx_scrambler_get_seed": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "pcx_scrambler_set_mode": (_i, [_vp, _i]),
+    "pcx_scrambler_get_mode": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_scrambler_get_plan": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_scrambler_get_geometry": (_i, [_psz, _psz, _psz, _psz]),
+    "pcx_scrambler_get_state": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pcx_scrambler_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_scrambler_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

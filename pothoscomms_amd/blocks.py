@@ -29,9 +29,11 @@ class PcxbLabel(C.Structure):
 _blib = None
 # the module libraries: "comms" is libpcx_blocks.so (comms_blocks.cpp, fir_designer.cpp), "filter" libpcx_filter_blocks.so
 # (filter_blocks.cpp: /comms/dc_removal), "envelope" libpcx_envelope_blocks.so (envelope_blocks.cpp: /comms/envelope_detector), "iir"
-# libpcx_iir_blocks.so (iir_blocks.cpp: /comms/iir_filter) -- one registry each, as Pothos loads one module library per source directory
+# libpcx_iir_blocks.so (iir_blocks.cpp: /comms/iir_filter), "digital" libpcx_digital_blocks.so (digital_blocks.cpp: /comms/scrambler,
+# /comms/descrambler) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
-           "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so")}
+           "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
+           "digital": os.path.join(_HERE, "libpcx_digital_blocks.so")}
 _mlibs = {}
 
 
@@ -67,6 +69,8 @@ def load(module="comms"):
     L.pcxb_call_double.argtypes = [vp, cp, C.c_double]
     L.pcxb_call_size.argtypes = [vp, cp, sz]
     L.pcxb_call_bool.argtypes = [vp, cp, i]
+    L.pcxb_call_int64.argtypes = [vp, cp, C.c_int64]
+    L.pcxb_get_int64.argtypes = [vp, cp, C.POINTER(C.c_int64)]
     L.pcxb_call_string.argtypes = [vp, cp, cp]
     L.pcxb_call_taps.argtypes = [vp, cp, vp, sz, i]
     L.pcxb_get_double.argtypes = [vp, cp, C.POINTER(C.c_double)]
@@ -232,6 +236,13 @@ class Block:
             v, cnt = (C.c_size_t * 64)(), C.c_size_t()
             _check_in(self._module, L.pcxb_get_sizes(self._h, n, v, 64, C.byref(cnt)))
             return [int(v[k]) for k in range(cnt.value)]
+        if name in ("setPoly", "setSeed"):      # int64_t, negative values included
+            v = int(args[0])
+            return _check_in(self._module, L.pcxb_call_int64(self._h, n, v - (1 << 64) if v >= (1 << 63) else v))
+        if name in ("poly", "seed") and not args:
+            v = C.c_int64()
+            _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
+            return v.value
         if not args:   # getter
             if name in ("getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
                         "getAverageSize", "getCascadeSize", "getLookahead"):

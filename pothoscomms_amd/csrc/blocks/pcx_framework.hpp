@@ -83,6 +83,7 @@ private:
         PCXFW_T(double, "float64") PCXFW_T(float, "float32") PCXFW_T(int64_t, "int64") PCXFW_T(int32_t, "int32")
         PCXFW_T(int16_t, "int16") PCXFW_T(int8_t, "int8")
 #undef PCXFW_T
+        if (t == typeid(unsigned char)) return "uint8";       // digital/Scrambler.cpp:47-48
         throw InvalidArgumentException("DType(typeid)", "unknown type");
     }
     void init(std::string n)

@@ -94,7 +94,7 @@ int pcxb_make(const char *path, const char *dtype, size_t dimension, const char 
     return guarded([&] {
         const std::string p(path);
         std::vector<Object> args;
-        const bool no_args = p == "/comms/fir_designer" || p == "/blocks/fir_designer";   // FIRDesigner::make(void)
+        const bool no_args = BlockRegistry::arity(p) == 0;   // FIRDesigner::make(void), Scrambler::make(void), Descrambler::make(void)
         if (!no_args) args.push_back(Object(DType(std::string(dtype), dimension ? dimension : 1)));
         if (no_args) {
         } else if (p == "/comms/fir_filter" || p == "/blocks/fir_filter" || p == "/comms/arithmetic" || p == "/blocks/arithmetic" ||
@@ -130,6 +130,7 @@ long pcxb_call_arity(pcxb_block *b, const char *name)
 
 int pcxb_call_double(pcxb_block *b, const char *name, double v) { return guarded([&] { b->blk->call(name, {Object(v)}); }); }
 int pcxb_call_size(pcxb_block *b, const char *name, size_t v) { return guarded([&] { b->blk->call(name, {Object((unsigned long)v)}); }); }
+int pcxb_call_int64(pcxb_block *b, const char *name, int64_t v) { return guarded([&] { b->blk->call(name, {Object((long long)v)}); }); }
 int pcxb_call_bool(pcxb_block *b, const char *name, int v) { return guarded([&] { b->blk->call(name, {Object(v != 0)}); }); }
 int pcxb_call_string(pcxb_block *b, const char *name, const char *v) { return guarded([&] { b->blk->call(name, {Object(std::string(v))}); }); }
 int pcxb_call_taps(pcxb_block *b, const char *name, const double *taps, size_t n, int is_complex)
@@ -158,6 +159,7 @@ int pcxb_get_sizes(pcxb_block *b, const char *name, size_t *out, size_t cap, siz
 }
 int pcxb_get_double(pcxb_block *b, const char *name, double *out) { return guarded([&] { *out = b->blk->call(name).convert<double>(); }); }
 int pcxb_get_size(pcxb_block *b, const char *name, size_t *out) { return guarded([&] { *out = b->blk->call(name).convert<unsigned long>(); }); }
+int pcxb_get_int64(pcxb_block *b, const char *name, int64_t *out) { return guarded([&] { *out = (int64_t)b->blk->call(name).convert<long long>(); }); }
 int pcxb_get_bool(pcxb_block *b, const char *name, int *out) { return guarded([&] { *out = b->blk->call(name).convert<bool>() ? 1 : 0; }); }
 int pcxb_get_string(pcxb_block *b, const char *name, char *out, size_t cap)
 {

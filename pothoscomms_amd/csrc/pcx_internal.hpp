@@ -264,6 +264,22 @@ int iir_history();          // inputs and outputs carried across calls (the larg
 // workspace of one slice
 int launch_iir_slice(const IirShape &p, const void *in, void *out, size_t m, void *xh, double *ystate, const double *tab, const double *coef,
                      double *z, double *tin, double *ytail, hipStream_t st);
+// (scrambler.hip) /comms/scrambler, /comms/descrambler: the register of a configured handle and one call slice
+struct ScrShape {
+    int descramble = 0;
+    int mode = PCX_SCR_MULTIPLICATIVE;
+    int plan = PCX_SCR_SCAN;
+    uint64_t polynomial = 0, mask = 0;      // lfsr_t's, as GLFSR_init leaves them
+    int m = 0;                              // the mask's lowest set bit
+};
+size_t scr_run();           // bits per thread, per tile, per wave of the carry, per slice
+size_t scr_tile();
+size_t scr_group();
+size_t scr_slice();
+// one slice of m bits; state[0]: the carried register, in and out (state[1]: workspace); pow: rows of M^(2^k), k < 27, 64 words each;
+// z, tin (one word per tile of a slice) and zl (64 per tile): workspace of the multiplicative plan
+int launch_scr_slice(const ScrShape &p, const void *in, void *out, size_t m, uint64_t *state, const uint64_t *pow, uint64_t *z, uint64_t *tin,
+                     uint64_t *zl, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

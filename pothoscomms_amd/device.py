@@ -434,6 +434,92 @@ class IIRFilter(_Handle):
         _lib.check(_lib.load().pcx_iir_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
 
 
+class Scrambler(_Handle):
+    """pcx_scrambler_*: digital/Scrambler.cpp's and Descrambler.cpp's loops over the Galois LFSR of digital/lfsr.h, bit for bit
+    (DESIGN.md 12).  One uint8 per bit in and out; only bit 0 of an input byte counts.
+
+    plan() says how the handle computes: SCR_SCAN when the polynomial owns the mask's lowest bit and the seed lies below it,
+    SCR_SERIAL (one thread, the reference's loop) otherwise.  state() is lfsr_t's (data, mask) after the last call."""
+    _destroy = "pcx_scrambler_destroy"
+    MODES = {"additive": _lib.SCR_ADDITIVE, "multiplicative": _lib.SCR_MULTIPLICATIVE}
+
+    def __init__(self, descramble=False, mode="multiplicative", poly=0x19, seed=1):
+        super().__init__()
+        self.descramble = bool(descramble)
+        _lib.check(_lib.load().pcx_scrambler_create(int(self.descramble), C.byref(self._h)))
+        self.set_mode(mode)
+        if seed != 1:
+            self.set_seed(seed)
+        if poly != 0x19:
+            self.set_poly(poly)
+
+    @staticmethod
+    def _i64(v):
+        v = int(v)
+        return v - (1 << 64) if v >= (1 << 63) else v          # 0x8000000000000003 is a negative int64_t
+
+    def set_poly(self, poly):
+        _lib.check(_lib.load().pcx_scrambler_set_poly(self._h, self._i64(poly)))
+
+    def set_seed(self, seed):
+        _lib.check(_lib.load().pcx_scrambler_set_seed(self._h, self._i64(seed)))
+
+    def set_mode(self, mode):
+        if mode not in self.MODES:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "Scrambler::set_mode(): unknown mode: %s" % (mode,))
+        _lib.check(_lib.load().pcx_scrambler_set_mode(self._h, self.MODES[mode]))
+
+    def poly(self):
+        v = C.c_int64()
+        _lib.check(_lib.load().pcx_scrambler_get_poly(self._h, C.byref(v)))
+        return v.value
+
+    def seed(self):
+        v = C.c_int64()
+        _lib.check(_lib.load().pcx_scrambler_get_seed(self._h, C.byref(v)))
+        return v.value
+
+    def mode(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_scrambler_get_mode(self._h, C.byref(v)))
+        return "additive" if v.value == _lib.SCR_ADDITIVE else "multiplicative"
+
+    def plan(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_scrambler_get_plan(self._h, C.byref(v)))
+        return v.value
+
+    def state(self):
+        """(data, mask) of the register as unsigned 64-bit integers, after the handle's last call"""
+        d, m = C.c_int64(), C.c_int64()
+        _lib.check(_lib.load().pcx_scrambler_get_state(self._h, C.byref(d), C.byref(m)))
+        return d.value & (2 ** 64 - 1), m.value & (2 ** 64 - 1)
+
+    @staticmethod
+    def geometry():
+        """(run, tile, group, slice): the bits a thread, a tile, a wave of the carry and a slice of the SCAN plan hold"""
+        v = [C.c_size_t() for _ in range(4)]
+        _lib.check(_lib.load().pcx_scrambler_get_geometry(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def process(self, x, out=None):
+        """x: (n,) uint8; returns the n output bytes (out=x works in place)"""
+        x = np.ascontiguousarray(x)
+        if x.dtype != np.uint8 or x.ndim != 1:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "scrambler: %s%s input for a uint8 block" % (x.dtype, x.shape))
+        if out is None:
+            y = np.zeros_like(x)
+        else:
+            y = out
+            if not (isinstance(y, np.ndarray) and y.dtype == x.dtype and y.shape == x.shape and y.flags.c_contiguous):
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "scrambler: out must be a contiguous uint8 array of shape %s" % (x.shape,))
+        _lib.check(_lib.load().pcx_scrambler_process(self._h, _np_ptr(x), _np_ptr(y), x.shape[0]))
+        return y
+
+    def process_dev(self, x, y, n, stream=None):
+        _lib.check(_lib.load().pcx_scrambler_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
