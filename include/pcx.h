@@ -425,6 +425,44 @@ PCX_API int pcx_scrambler_process(pcx_scrambler *h, const void *in, void *out, s
 PCX_API int pcx_scrambler_process_dev(pcx_scrambler *h, const void *in_dev, void *out_dev, size_t n, void *stream);
 
 /* ===================================================================== *
+ *  /comms/preamble_correlator      digital/PreambleCorrelator.cpp
+ *
+ *  One unsigned char per symbol.  For every position n < n_in - P the Hamming distance over whole bytes,
+ *  dist[n] = sum over i < P of popcount(preamble[i] ^ in[n + i]) (:134-143): the upper bits of an input byte count.  A position
+ *  with dist <= threshold is a match and its label index is n + P (:145-148), which may lie up to P - 1 past the last position.
+ *  Every index, count and distance equals the reference's.  Nothing is carried from one call to the next.
+ * ===================================================================== */
+typedef struct pcx_preamble pcx_preamble;
+/* pcx_preamble_get_plan: how a configured handle computes the distances -- per bit plane of the symbols (preambles of up to
+ * max_planes_len symbols, pcx_preamble_get_geometry), or the reference's byte loop, one position per thread (longer ones) */
+enum { PCX_PRE_PLANES = 0, PCX_PRE_BYTES = 1 };
+/* the constructor (:60-75): preamble {1}, threshold 1.  Where a device can be reached the workspace of one slice is allocated and
+ * the packed preamble uploaded here and in set_preamble; otherwise at the first call that computes. */
+PCX_API int pcx_preamble_create(pcx_preamble **out);
+PCX_API int pcx_preamble_destroy(pcx_preamble *h);
+/* setPreamble (:77-81): n == 0 is PCX_ERR_ARG "preamble cannot be empty" */
+PCX_API int pcx_preamble_set_preamble(pcx_preamble *h, const unsigned char *symbols, size_t n);
+/* *n = the preamble's length; the first min(*n, cap) symbols go to out (out may be NULL when cap is 0) */
+PCX_API int pcx_preamble_get_preamble(const pcx_preamble *h, unsigned char *out, size_t cap, size_t *n);
+PCX_API int pcx_preamble_set_threshold(pcx_preamble *h, unsigned threshold);
+PCX_API int pcx_preamble_get_threshold(const pcx_preamble *h, unsigned *threshold);
+PCX_API int pcx_preamble_get_plan(const pcx_preamble *h, int *plan);
+/* positions a workgroup and a call slice hold (the seams a test wants to straddle), and the longest preamble of the PLANES plan */
+PCX_API int pcx_preamble_get_geometry(size_t *tile, size_t *slice, size_t *max_planes_len);
+/* work() (:114-154) on in[0 .. n_in): *n_positions = n_in > P ? n_in - P : 0; idx receives the label indices n + P in ascending
+ * order, the first min(*n_matches, idx_cap) of them; *n_matches is always the full count.  out, when not NULL, receives the first
+ * *n_positions input bytes (out == in is allowed, any other overlap is PCX_ERR_ARG).  Checked in this order before any device
+ * call: the handle, the two counts.  process_dev takes device pointers throughout, the two counts included, allocates nothing
+ * and synchronises nothing: it can be captured into a graph. */
+PCX_API int pcx_preamble_process(pcx_preamble *h, const void *in, size_t n_in, void *out, uint64_t *idx, size_t idx_cap, size_t *n_positions,
+                                 size_t *n_matches);
+PCX_API int pcx_preamble_process_dev(pcx_preamble *h, const void *in_dev, size_t n_in, void *out_dev, uint64_t *idx_dev, size_t idx_cap,
+                                     uint64_t *n_positions_dev, uint64_t *n_matches_dev, void *stream);
+/* dist[n] for every position (the reference's commented-out second port, :65, :133, :150): dist holds n_in - P words */
+PCX_API int pcx_preamble_distances(pcx_preamble *h, const void *in, size_t n_in, uint32_t *dist, size_t *n_positions);
+PCX_API int pcx_preamble_distances_dev(pcx_preamble *h, const void *in_dev, size_t n_in, uint32_t *dist_dev, void *stream);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

@@ -59,6 +59,10 @@ PCXB_API int pcxb_call_string(pcxb_block *b, const char *name, const char *v);
 PCXB_API int pcxb_call_taps(pcxb_block *b, const char *name, const double *taps, size_t n, int is_complex);
 PCXB_API int pcxb_call_sizes(pcxb_block *b, const char *name, const size_t *v, size_t n);   /* std::vector<size_t> (setPreload) */
 PCXB_API int pcxb_get_sizes(pcxb_block *b, const char *name, size_t *out, size_t cap, size_t *n);
+/* std::vector<unsigned char> (setPreamble / getPreamble of /comms/preamble_correlator); *n = the vector's length, the first min(*n, cap)
+ * bytes go to out.  An unsigned argument (setThreshold) travels through pcxb_call_size / pcxb_get_size. */
+PCXB_API int pcxb_call_bytes(pcxb_block *b, const char *name, const unsigned char *v, size_t n);
+PCXB_API int pcxb_get_bytes(pcxb_block *b, const char *name, unsigned char *out, size_t cap, size_t *n);
 PCXB_API int pcxb_get_double(pcxb_block *b, const char *name, double *out);
 PCXB_API int pcxb_get_size(pcxb_block *b, const char *name, size_t *out);
 PCXB_API int pcxb_get_int64(pcxb_block *b, const char *name, int64_t *out);

@@ -20,6 +20,7 @@ FIR_AUTO, FIR_DIRECT, FIR_OLS_FFT, FIR_EXACT = 0, 1, 2, 3
 IIR_SCAN, IIR_SERIAL = 0, 1          # pcx_iir_get_plan
 SCR_ADDITIVE, SCR_MULTIPLICATIVE = 0, 1     # pcx_scrambler_set_mode
 SCR_SCAN, SCR_SERIAL = 0, 1          # pcx_scrambler_get_plan
+PRE_PLANES, PRE_BYTES = 0, 1         # pcx_preamble_get_plan
 
 
 class PcxError(RuntimeError):
@@ -152,6 +153,18 @@ SIGNATURES = {
     "pcx_scrambler_get_state": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcx_scrambler_process": (_i, [_vp, _vp, _vp, _sz]),
     "pcx_scrambler_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_preamble_create": (_i, [C.POINTER(_vp)]),
+    "pcx_preamble_destroy": (_i, [_vp]),
+    "pcx_preamble_set_preamble": (_i, [_vp, _vp, _sz]),
+    "pcx_preamble_get_preamble": (_i, [_vp, _vp, _sz, _psz]),
+    "pcx_preamble_set_threshold": (_i, [_vp, C.c_uint]),
+    "pcx_preamble_get_threshold": (_i, [_vp, C.POINTER(C.c_uint)]),
+    "pcx_preamble_get_plan": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_preamble_get_geometry": (_i, [_psz, _psz, _psz]),
+    "pcx_preamble_process": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _psz, _psz]),
+    "pcx_preamble_process_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "pcx_preamble_distances": (_i, [_vp, _vp, _sz, _vp, _psz]),
+    "pcx_preamble_distances_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

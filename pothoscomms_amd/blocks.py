@@ -30,10 +30,11 @@ _blib = None
 # the module libraries: "comms" is libpcx_blocks.so (comms_blocks.cpp, fir_designer.cpp), "filter" libpcx_filter_blocks.so
 # (filter_blocks.cpp: /comms/dc_removal), "envelope" libpcx_envelope_blocks.so (envelope_blocks.cpp: /comms/envelope_detector), "iir"
 # libpcx_iir_blocks.so (iir_blocks.cpp: /comms/iir_filter), "digital" libpcx_digital_blocks.so (digital_blocks.cpp: /comms/scrambler,
-# /comms/descrambler) -- one registry each, as Pothos loads one module library per source directory
+# /comms/descrambler), "correlator" libpcx_correlator_blocks.so (correlator_blocks.cpp: /comms/preamble_correlator) -- one registry each,
+# as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
-           "digital": os.path.join(_HERE, "libpcx_digital_blocks.so")}
+           "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so")}
 _mlibs = {}
 
 
@@ -71,6 +72,8 @@ def load(module="comms"):
     L.pcxb_call_bool.argtypes = [vp, cp, i]
     L.pcxb_call_int64.argtypes = [vp, cp, C.c_int64]
     L.pcxb_get_int64.argtypes = [vp, cp, C.POINTER(C.c_int64)]
+    L.pcxb_call_bytes.argtypes = [vp, cp, vp, sz]
+    L.pcxb_get_bytes.argtypes = [vp, cp, vp, sz, C.POINTER(sz)]
     L.pcxb_call_string.argtypes = [vp, cp, cp]
     L.pcxb_call_taps.argtypes = [vp, cp, vp, sz, i]
     L.pcxb_get_double.argtypes = [vp, cp, C.POINTER(C.c_double)]
@@ -243,8 +246,15 @@ class Block:
             v = C.c_int64()
             _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
             return v.value
+        if name == "setPreamble":               # std::vector<unsigned char>
+            v = np.ascontiguousarray(np.asarray(args[0], dtype=np.uint8).reshape(-1))
+            return _check_in(self._module, L.pcxb_call_bytes(self._h, n, v.ctypes.data_as(C.c_void_p) if v.size else None, v.size))
+        if name == "getPreamble":
+            buf, cnt = np.zeros(1 << 16, np.uint8), C.c_size_t()
+            _check_in(self._module, L.pcxb_get_bytes(self._h, n, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(cnt)))
+            return [int(b) for b in buf[:cnt.value]]
         if not args:   # getter
-            if name in ("getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
+            if name in ("getThreshold", "getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
                         "getAverageSize", "getCascadeSize", "getLookahead"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
@@ -374,9 +384,10 @@ class Block:
         produced = [int(v) for v in prod]
         return [y[:p * port[2]] for y, p, port in zip(ys, produced, op)], [int(v) for v in cons], produced
 
-    def work(self, inbuf, out_elems, labels=(), outbuf=None):
+    def work(self, inbuf, out_elems, labels=(), outbuf=None, label_cap=64):
         """One work() call.  Returns (out[:produced], consumed, produced, reserve, posted_labels).
-        outbuf: write into this array (e.g. a slab from port_buffer) instead of a fresh one."""
+        outbuf: write into this array (e.g. a slab from port_buffer) instead of a fresh one.
+        label_cap: how many posted labels come back at most (a correlator can post one per symbol)."""
         x = as_pairs(inbuf)
         scalar, cplx = parse_dtype(self.out_dtype)
         shape = [out_elems * self.out_dim] + ([2] if cplx else [])
@@ -389,14 +400,14 @@ class Block:
         labs = (PcxbLabel * max(1, len(labels)))()
         for i, l in enumerate(labels):
             l._to_c(labs[i])
-        posted = (PcxbLabel * 64)()
+        posted = (PcxbLabel * label_cap)()
         c, p, r, npost = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         _check_in(self._module, load(self._module).pcxb_work(self._h, x.ctypes.data_as(C.c_void_p), in_elems, labs, len(labels),
                                 y.ctypes.data_as(C.c_void_p), out_elems, C.byref(c), C.byref(p), C.byref(r),
-                                posted, 64, C.byref(npost)))
+                                posted, label_cap, C.byref(npost)))
         reserve = None if r.value == _SIZE_MAX else r.value
         return (y[:p.value * self.out_dim], c.value, p.value, reserve,
-                [Label._from_c(posted[i]) for i in range(min(npost.value, 64))])
+                [Label._from_c(posted[i]) for i in range(min(npost.value, label_cap))])
 
 
 class CircularBuffer:

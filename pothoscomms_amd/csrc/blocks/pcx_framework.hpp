@@ -127,6 +127,7 @@ public:
     Object(const std::vector<double> &v) : _t(&typeid(std::vector<double>)), _vd(v) {}
     Object(const std::vector<std::complex<double>> &v) : _t(&typeid(std::vector<std::complex<double>>)), _vc(v) {}
     Object(const std::vector<size_t> &v) : _t(&typeid(std::vector<size_t>)), _vs(v) {}
+    Object(const std::vector<unsigned char> &v) : _t(&typeid(std::vector<unsigned char>)), _vb(v) {}     // digital/PreambleCorrelator.cpp:77
 
     const std::type_info &type() const { return *_t; }
     bool isNumber() const
@@ -177,6 +178,7 @@ private:
         if (*_t == typeid(std::vector<double>)) return std::vector<size_t>(_vd.begin(), _vd.end());
         return _vs;
     }
+    std::vector<unsigned char> get(std::vector<unsigned char> *) const { return _vb; }
     const std::type_info *_t;
     double _d = 0;
     long long _i = 0;
@@ -184,6 +186,7 @@ private:
     std::vector<double> _vd;
     std::vector<std::complex<double>> _vc;
     std::vector<size_t> _vs;
+    std::vector<unsigned char> _vb;
 };
 
 // ---- BufferChunk: a view (optionally owning) of typed memory ----

@@ -94,7 +94,7 @@ int pcxb_make(const char *path, const char *dtype, size_t dimension, const char 
     return guarded([&] {
         const std::string p(path);
         std::vector<Object> args;
-        const bool no_args = BlockRegistry::arity(p) == 0;   // FIRDesigner::make(void), Scrambler::make(void), Descrambler::make(void)
+        const bool no_args = BlockRegistry::arity(p) == 0;   // FIRDesigner::make(void), Scrambler::make(void), Descrambler::make(void), PreambleCorrelator::make(void)
         if (!no_args) args.push_back(Object(DType(std::string(dtype), dimension ? dimension : 1)));
         if (no_args) {
         } else if (p == "/comms/fir_filter" || p == "/blocks/fir_filter" || p == "/comms/arithmetic" || p == "/blocks/arithmetic" ||
@@ -153,6 +153,18 @@ int pcxb_get_sizes(pcxb_block *b, const char *name, size_t *out, size_t cap, siz
 {
     return guarded([&] {
         const auto v = b->blk->call(name).convert<std::vector<size_t>>();
+        *n = v.size();
+        for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
+    });
+}
+int pcxb_call_bytes(pcxb_block *b, const char *name, const unsigned char *v, size_t n)
+{
+    return guarded([&] { b->blk->call(name, {Object(n ? std::vector<unsigned char>(v, v + n) : std::vector<unsigned char>())}); });
+}
+int pcxb_get_bytes(pcxb_block *b, const char *name, unsigned char *out, size_t cap, size_t *n)
+{
+    return guarded([&] {
+        const auto v = b->blk->call(name).convert<std::vector<unsigned char>>();
         *n = v.size();
         for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
     });

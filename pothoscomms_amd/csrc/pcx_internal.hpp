@@ -280,6 +280,28 @@ size_t scr_slice();
 // z, tin (one word per tile of a slice) and zl (64 per tile): workspace of the multiplicative plan
 int launch_scr_slice(const ScrShape &p, const void *in, void *out, size_t m, uint64_t *state, const uint64_t *pow, uint64_t *z, uint64_t *tin,
                      uint64_t *zl, hipStream_t st);
+// (preamble.hip) /comms/preamble_correlator: a configured preamble and one call slice
+struct PreShape {
+    size_t P = 1;                           // preamble symbols
+    uint32_t active = 1;                    // bit b: the preamble has a set bit in plane b
+    uint32_t threshold = 1;
+    int plan = PCX_PRE_PLANES;
+};
+struct PreWork {                            // workspace of one slice: one match bit per position, matches per tile, those in front of a tile;
+    uint32_t *mask = nullptr, *counts = nullptr, *toff = nullptr;
+    uint64_t *state = nullptr;              // [0] matches of the call so far, [1] those in front of the slice
+};
+size_t pre_tile();                          // positions per workgroup, per slice
+size_t pre_slice();
+size_t pre_max_planes_len();                // the longest preamble of the PLANES plan
+size_t pre_table_words();                   // packed preamble: 8 planes of this many / 8 words, bit i of word k = symbol 32 k + i
+// one slice of m positions from in[0] (in[0 .. m + P) exists), pos0 positions into the call: the first min(matches, cap) label indices
+// pos0 + n + P go to idx behind those of the earlier slices, out (or null) receives the m bytes; first: the call's first slice; the
+// last slice passes the device words that receive the call's counts (else null)
+int launch_pre_slice(const PreShape &p, const void *in, void *out, size_t m, const uint32_t *pw, const unsigned char *pre, const PreWork &w, uint64_t pos0,
+                     int first, uint64_t npos, uint64_t *npos_out, uint64_t *nmatch_out, uint64_t *idx, uint64_t cap, hipStream_t st);
+int launch_pre_empty(uint64_t *state, uint64_t *npos_out, uint64_t *nmatch_out, hipStream_t st);
+int launch_pre_distances(const PreShape &p, const void *in, size_t m, const uint32_t *pw, const unsigned char *pre, uint32_t *dist, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

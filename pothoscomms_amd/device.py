@@ -520,6 +520,94 @@ class Scrambler(_Handle):
         _lib.check(_lib.load().pcx_scrambler_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
 
 
+class PreambleCorrelator(_Handle):
+    """pcx_preamble_*: digital/PreambleCorrelator.cpp's search -- the Hamming distance between the preamble and the input at every
+    position, over whole bytes, and the positions where it does not exceed the threshold.  One uint8 per symbol.
+
+    plan() says how the handle computes the distances: PRE_PLANES per bit plane of the symbols, PRE_BYTES (preambles beyond
+    geometry()[2] symbols) the reference's byte loop with one position per thread."""
+    _destroy = "pcx_preamble_destroy"
+
+    def __init__(self, preamble=(1,), threshold=1):
+        super().__init__()
+        _lib.check(_lib.load().pcx_preamble_create(C.byref(self._h)))
+        if tuple(preamble) != (1,):
+            self.set_preamble(preamble)
+        if threshold != 1:
+            self.set_threshold(threshold)
+
+    def set_preamble(self, preamble):
+        p = np.ascontiguousarray(np.asarray(preamble, dtype=np.uint8).reshape(-1))
+        _lib.check(_lib.load().pcx_preamble_set_preamble(self._h, _np_ptr(p) if p.size else None, p.size))
+
+    def preamble(self):
+        n = C.c_size_t()
+        _lib.check(_lib.load().pcx_preamble_get_preamble(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        _lib.check(_lib.load().pcx_preamble_get_preamble(self._h, _np_ptr(out), out.size, C.byref(n)))
+        return out
+
+    def set_threshold(self, threshold):
+        _lib.check(_lib.load().pcx_preamble_set_threshold(self._h, int(threshold)))
+
+    def threshold(self):
+        v = C.c_uint()
+        _lib.check(_lib.load().pcx_preamble_get_threshold(self._h, C.byref(v)))
+        return v.value
+
+    def plan(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_preamble_get_plan(self._h, C.byref(v)))
+        return v.value
+
+    @staticmethod
+    def geometry():
+        """(tile, slice, max_planes_len): the positions a workgroup and a call slice hold, and the longest preamble of the PLANES plan"""
+        v = [C.c_size_t() for _ in range(3)]
+        _lib.check(_lib.load().pcx_preamble_get_geometry(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @staticmethod
+    def _symbols(x):
+        x = np.ascontiguousarray(x)
+        if x.dtype != np.uint8 or x.ndim != 1:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "preamble correlator: %s%s input for a uint8 block" % (x.dtype, x.shape))
+        return x
+
+    def process(self, x, cap=None, out=None):
+        """x: (n,) uint8 -> (label indices n + P as uint64, n_positions, n_matches).  At most `cap` indices come back (default: every
+        position could match); n_matches is the full count.  out: a uint8 array that receives the n_positions forwarded bytes."""
+        x = self._symbols(x)
+        P = self.preamble().size
+        cap = max(0, x.shape[0] - P) if cap is None else int(cap)
+        idx = np.zeros(max(cap, 1), np.uint64)
+        npos, nm = C.c_size_t(), C.c_size_t()
+        if out is not None and not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
+                                    and out.size >= max(0, x.shape[0] - P)):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "preamble correlator: out must be a contiguous uint8 array of n - P elements")
+        _lib.check(_lib.load().pcx_preamble_process(self._h, _np_ptr(x), x.shape[0], None if out is None else _np_ptr(out), _np_ptr(idx), cap,
+                                                    C.byref(npos), C.byref(nm)))
+        return idx[:min(nm.value, cap)].copy(), npos.value, nm.value
+
+    def distances(self, x):
+        """x: (n,) uint8 -> the n - P Hamming distances as uint32"""
+        x = self._symbols(x)
+        d = np.zeros(max(1, x.shape[0] - self.preamble().size), np.uint32)
+        npos = C.c_size_t()
+        _lib.check(_lib.load().pcx_preamble_distances(self._h, _np_ptr(x), x.shape[0], _np_ptr(d), C.byref(npos)))
+        return d[:npos.value]
+
+    def process_dev(self, x, n_in, idx, cap, counts, out=None, stream=None):
+        """device tensors: x uint8, idx int64 / uint64 of at least cap elements, counts two 64-bit words that receive (n_positions,
+        n_matches), out uint8 or None; nothing is allocated or synchronised"""
+        c = _dev_ptr(counts).value
+        _lib.check(_lib.load().pcx_preamble_process_dev(self._h, _dev_ptr(x), n_in, None if out is None else _dev_ptr(out),
+                                                        _dev_ptr(idx) if cap else None, cap, C.c_void_p(c), C.c_void_p(c + 8), _stream_ptr(stream)))
+
+    def distances_dev(self, x, n_in, dist, stream=None):
+        _lib.check(_lib.load().pcx_preamble_distances_dev(self._h, _dev_ptr(x), n_in, _dev_ptr(dist), _stream_ptr(stream)))
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
