@@ -463,6 +463,83 @@ PCX_API int pcx_preamble_distances(pcx_preamble *h, const void *in, size_t n_in,
 PCX_API int pcx_preamble_distances_dev(pcx_preamble *h, const void *in_dev, size_t n_in, uint32_t *dist_dev, void *stream);
 
 /* ===================================================================== *
+ *  /comms/symbol_mapper      digital/SymbolMapper.cpp
+ *
+ *  out[i] = map[in[i] & mask] (:89-91): one unsigned char in, one element of the stream type out.  Exact.
+ * ===================================================================== */
+typedef struct pcx_mapper pcx_mapper;
+/* SymbolMapperFactory(dtype), :106-122: scalar in {F64, F32, I64, I32, I16, I8}, real or complex; anything else is PCX_ERR_ARG
+ * "unsupported type".  The constructor's map is {1} (:58). */
+PCX_API int pcx_mapper_create(int scalar, int is_complex, pcx_mapper **out);
+PCX_API int pcx_mapper_destroy(pcx_mapper *h);
+/* setMap (:66-77): n elements in the stream type's own layout (an int64 map is exact; complex is re, im interleaved).  Checked in this
+ * order: the handle, n == 0 "Map must be nonzero size", n not a power of two "Map must be a power of two in length", a null map.
+ * mask = (unsigned char)((1 << log2(n)) - 1): a map of 512 entries has mask 255 and uses its first 256, a map of 1 entry mask 0. */
+PCX_API int pcx_mapper_set_map(pcx_mapper *h, const void *map, size_t n);
+/* *n = the map's length; the first min(*n, cap) elements go to out (out may be NULL when cap is 0) */
+PCX_API int pcx_mapper_get_map(const pcx_mapper *h, void *out, size_t cap, size_t *n);
+/* work()'s loop (:79-95) over n elements.  Checked in this order before any device call: the handle, n == 0 (nothing to do), null
+ * buffers, any overlap of the n input bytes with the output.  process_dev synchronises nothing and allocates nothing: it can be
+ * captured into a graph.  The reference counts the elements of a call in 32 bits; n here is a size_t and is not truncated. */
+PCX_API int pcx_mapper_process(pcx_mapper *h, const void *in, void *out, size_t n);
+PCX_API int pcx_mapper_process_dev(pcx_mapper *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+
+/* ===================================================================== *
+ *  /comms/symbol_slicer      digital/SymbolSlicer.cpp
+ *
+ *  out[i] = the index, stored into an unsigned char, of the first map entry whose float distance to in[i] is strictly smallest,
+ *  starting from (0, FLT_MAX) (:88-97).  Real types: (float)abs(map[j] - in[i]) in the promoted element type (:43-46); complex types:
+ *  the two differences converted to float, two rounded products and one rounded sum (:49-52).  Exact; int32 / int64 differences that
+ *  leave the signed type wrap, where the reference is undefined.
+ * ===================================================================== */
+typedef struct pcx_slicer pcx_slicer;
+/* SymbolSlicerFactory(dtype), :111-127: the mapper's type matrix.  The constructor's map is {1} (:64). */
+PCX_API int pcx_slicer_create(int scalar, int is_complex, pcx_slicer **out);
+PCX_API int pcx_slicer_destroy(pcx_slicer *h);
+/* setMap (:72-76): n elements in the stream type's own layout, any n but 0 ("Map must be nonzero size"; then a null map; the handle
+ * first) */
+PCX_API int pcx_slicer_set_map(pcx_slicer *h, const void *map, size_t n);
+PCX_API int pcx_slicer_get_map(const pcx_slicer *h, void *out, size_t cap, size_t *n);
+/* samples a lane and a workgroup hold, the longest map of the on-chip plan (longer ones are read from global memory) and the elements
+ * of a call slice: the seams a test wants to straddle */
+PCX_API int pcx_slicer_get_geometry(const pcx_slicer *h, size_t *lane, size_t *group, size_t *max_onchip_map, size_t *slice);
+/* work()'s loop (:78-101) over n elements; checks and graph capture as pcx_mapper_process (the overlap is that of the input elements
+ * with the n output bytes) */
+PCX_API int pcx_slicer_process(pcx_slicer *h, const void *in, void *out, size_t n);
+PCX_API int pcx_slicer_process_dev(pcx_slicer *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+
+/* ===================================================================== *
+ *  /comms/differential_encoder, /comms/differential_decoder      digital/DifferentialEncoder.cpp, digital/DifferentialDecoder.cpp
+ *
+ *  One unsigned char per symbol in and out, a uint32_t symbols (2 at first) and a carried byte (0 at first) that survives calls and
+ *  set_symbols.  Encoder (:59-63): last = (uint8_t)((in[i] + last + symbols) % symbols) in uint32_t, out[i] = last.  Decoder (:59-64):
+ *  out[i] = (uint8_t)((in[i] - in[i-1] + symbols) % symbols) in uint32_t, in[-1] the carried byte.  Exact.
+ * ===================================================================== */
+typedef struct pcx_diffcode pcx_diffcode;
+/* pcx_diffcode_get_plan: SCAN when the encoder's step equals (in + last) mod min(symbols, 256) for all 65536 byte pairs (checked in
+ * set_symbols), SERIAL (one thread, the reference's loop) otherwise; the decoder always reports SCAN */
+enum { PCX_DIFF_SCAN = 0, PCX_DIFF_SERIAL = 1 };
+/* decode = 0 the encoder, otherwise the decoder (:30 of either file) */
+PCX_API int pcx_diffcode_create(int decode, pcx_diffcode **out);
+PCX_API int pcx_diffcode_destroy(pcx_diffcode *h);
+/* setSymbols (:37-40).  DEVIATION: symbols == 0 (a division by zero in the reference) is PCX_ERR_ARG "symbols cannot be 0", checked
+ * after the handle; the previous value is kept.  The carried byte is left alone. */
+PCX_API int pcx_diffcode_set_symbols(pcx_diffcode *h, uint32_t symbols);
+PCX_API int pcx_diffcode_get_symbols(const pcx_diffcode *h, uint32_t *symbols);
+PCX_API int pcx_diffcode_get_plan(const pcx_diffcode *h, int *plan);
+/* bytes a workgroup and a call slice hold (the seams a test wants to straddle) */
+PCX_API int pcx_diffcode_get_geometry(size_t *tile, size_t *slice);
+/* the carried byte after the handle's last call (waits for it) */
+PCX_API int pcx_diffcode_get_state(pcx_diffcode *h, unsigned char *last);
+/* the carried byte back to 0 (for API users: the blocks never call it, as the reference has no activate()) */
+PCX_API int pcx_diffcode_reset(pcx_diffcode *h);
+/* work()'s loop over n bytes, the byte carried across calls.  out may be in itself (in place); any other overlap is PCX_ERR_ARG.
+ * Checked in this order before any device call: the handle, n == 0, null buffers, the overlap.  process_dev synchronises nothing and
+ * allocates nothing: it can be captured into a graph.  n is a size_t and is not truncated to 32 bits as the reference's count is. */
+PCX_API int pcx_diffcode_process(pcx_diffcode *h, const void *in, void *out, size_t n);
+PCX_API int pcx_diffcode_process_dev(pcx_diffcode *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

@@ -21,6 +21,7 @@ IIR_SCAN, IIR_SERIAL = 0, 1          # pcx_iir_get_plan
 SCR_ADDITIVE, SCR_MULTIPLICATIVE = 0, 1     # pcx_scrambler_set_mode
 SCR_SCAN, SCR_SERIAL = 0, 1          # pcx_scrambler_get_plan
 PRE_PLANES, PRE_BYTES = 0, 1         # pcx_preamble_get_plan
+DIFF_SCAN, DIFF_SERIAL = 0, 1        # pcx_diffcode_get_plan
 
 
 class PcxError(RuntimeError):
@@ -165,6 +166,29 @@ SIGNATURES = {
     "pcx_preamble_process_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "pcx_preamble_distances": (_i, [_vp, _vp, _sz, _vp, _psz]),
     "pcx_preamble_distances_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "pcx_mapper_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "pcx_mapper_destroy": (_i, [_vp]),
+    "pcx_mapper_set_map": (_i, [_vp, _vp, _sz]),
+    "pcx_mapper_get_map": (_i, [_vp, _vp, _sz, _psz]),
+    "pcx_mapper_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_mapper_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_slicer_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "pcx_slicer_destroy": (_i, [_vp]),
+    "pcx_slicer_set_map": (_i, [_vp, _vp, _sz]),
+    "pcx_slicer_get_map": (_i, [_vp, _vp, _sz, _psz]),
+    "pcx_slicer_get_geometry": (_i, [_vp, _psz, _psz, _psz, _psz]),
+    "pcx_slicer_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_slicer_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_diffcode_create": (_i, [_i, C.POINTER(_vp)]),
+    "pcx_diffcode_destroy": (_i, [_vp]),
+    "pcx_diffcode_set_symbols": (_i, [_vp, C.c_uint32]),
+    "pcx_diffcode_get_symbols": (_i, [_vp, C.POINTER(C.c_uint32)]),
+    "pcx_diffcode_get_plan": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_diffcode_get_geometry": (_i, [_psz, _psz]),
+    "pcx_diffcode_get_state": (_i, [_vp, C.POINTER(C.c_ubyte)]),
+    "pcx_diffcode_reset": (_i, [_vp]),
+    "pcx_diffcode_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_diffcode_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

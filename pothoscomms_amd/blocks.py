@@ -30,11 +30,13 @@ _blib = None
 # the module libraries: "comms" is libpcx_blocks.so (comms_blocks.cpp, fir_designer.cpp), "filter" libpcx_filter_blocks.so
 # (filter_blocks.cpp: /comms/dc_removal), "envelope" libpcx_envelope_blocks.so (envelope_blocks.cpp: /comms/envelope_detector), "iir"
 # libpcx_iir_blocks.so (iir_blocks.cpp: /comms/iir_filter), "digital" libpcx_digital_blocks.so (digital_blocks.cpp: /comms/scrambler,
-# /comms/descrambler), "correlator" libpcx_correlator_blocks.so (correlator_blocks.cpp: /comms/preamble_correlator) -- one registry each,
-# as Pothos loads one module library per source directory
+# /comms/descrambler), "correlator" libpcx_correlator_blocks.so (correlator_blocks.cpp: /comms/preamble_correlator), "symbol"
+# libpcx_symbol_blocks.so (symbol_blocks.cpp: /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder,
+# /comms/differential_decoder) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
-           "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so")}
+           "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
+           "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so")}
 _mlibs = {}
 
 
@@ -214,12 +216,12 @@ class Block:
     # ---- registered calls ----
     def call(self, name, *args):
         L, n = load(self._module), name.encode()
-        if name == "setTaps":
+        if name in ("setTaps", "setMap"):       # setMap: a symbol map, real or complex, as doubles (an int64 value beyond 2^53 needs the C ABI)
             t = np.asarray(args[0])
             cplx = np.iscomplexobj(t)
             flat = np.ascontiguousarray(t.astype(np.complex128)).view(np.float64) if cplx else np.ascontiguousarray(t.astype(np.float64))
             return _check_in(self._module, L.pcxb_call_taps(self._h, n, flat.ctypes.data_as(C.c_void_p), t.size, int(cplx)))
-        if name == "getTaps":
+        if name in ("getTaps", "getMap"):
             cplx = bool(args[0]) if args else False
             buf = np.zeros(1 << 16, np.float64)
             cnt = C.c_size_t()
@@ -255,7 +257,7 @@ class Block:
             return [int(b) for b in buf[:cnt.value]]
         if not args:   # getter
             if name in ("getThreshold", "getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
-                        "getAverageSize", "getCascadeSize", "getLookahead"):
+                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value

@@ -302,6 +302,23 @@ int launch_pre_slice(const PreShape &p, const void *in, void *out, size_t m, con
                      int first, uint64_t npos, uint64_t *npos_out, uint64_t *nmatch_out, uint64_t *idx, uint64_t cap, hipStream_t st);
 int launch_pre_empty(uint64_t *state, uint64_t *npos_out, uint64_t *nmatch_out, hipStream_t st);
 int launch_pre_distances(const PreShape &p, const void *in, size_t m, const uint32_t *pw, const unsigned char *pre, uint32_t *dist, hipStream_t st);
+// (symbols.hip) /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder, /comms/differential_decoder
+struct DiffShape {
+    int decode = 0;
+    uint32_t symbols = 2;
+    int plan = PCX_DIFF_SCAN;
+};
+size_t sym_tile();                          // bytes per workgroup of the mapper and the coders, elements per call slice
+size_t sym_slice();
+size_t slicer_max_onchip();                 // the longest map the slicer holds in LDS
+size_t slicer_lane_samples(int scalar, bool cplx);
+size_t slicer_block_samples(int scalar, bool cplx);
+// tab: 256 elements of the stream type, entry b = map[b & mask]
+int launch_sym_map(int scalar, bool cplx, const void *in, void *out, size_t m, const void *tab, hipStream_t st);
+// mapc: M entries in the promoted type (int for int8 / int16 / int32, long for int64, float, double), complex interleaved
+int launch_sym_slice(int scalar, bool cplx, const void *in, void *out, size_t m, const void *mapc, size_t M, hipStream_t st);
+// one slice of m bytes; state[0]: the carried byte, in and out; tsum, tin: one word per tile of a slice
+int launch_diff_slice(const DiffShape &p, const void *in, void *out, size_t m, uint32_t *state, uint32_t *tsum, uint32_t *tin, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

@@ -608,6 +608,157 @@ class PreambleCorrelator(_Handle):
         _lib.check(_lib.load().pcx_preamble_distances_dev(self._h, _dev_ptr(x), n_in, _dev_ptr(dist), _stream_ptr(stream)))
 
 
+class _SymbolMap(_Handle):
+    """what pcx_mapper_* and pcx_slicer_* share: a map in the stream type's own element layout"""
+    _family = None
+
+    def __init__(self, dtype="complex_float32", map=None):
+        super().__init__()
+        self.scalar, self.is_complex = parse_dtype(dtype)
+        _lib.check(getattr(_lib.load(), self._family + "_create")(self.scalar, int(self.is_complex), C.byref(self._h)))
+        if map is not None:
+            self.set_map(map)
+
+    def _typed(self, m):
+        """a map as an array of the stream type: (n,) for a real stream, (n, 2) for a complex one.  An array that already has the
+        stream's scalar type is taken as it is (so an int64 map is exact); anything else goes through complex128 / float64."""
+        t = NP_SCALAR[self.scalar]
+        a = np.asarray(m)
+        if self.is_complex:
+            if a.dtype == t and a.ndim == 2 and a.shape[1] == 2:
+                return np.ascontiguousarray(a)
+            c = a.astype(np.complex128).reshape(-1)
+            return np.ascontiguousarray(np.stack([c.real, c.imag], axis=1).astype(t))
+        if a.dtype == t:
+            return np.ascontiguousarray(a.reshape(-1))
+        return np.ascontiguousarray(np.real(a).astype(np.float64).astype(t).reshape(-1))
+
+    def set_map(self, m):
+        a = self._typed(m)
+        _lib.check(getattr(_lib.load(), self._family + "_set_map")(self._h, _np_ptr(a) if a.size else None, a.shape[0]))
+
+    def map(self):
+        """the map as last set, in the stream type: (n,) or (n, 2)"""
+        n = C.c_size_t()
+        get = getattr(_lib.load(), self._family + "_get_map")
+        _lib.check(get(self._h, None, 0, C.byref(n)))
+        a = np.zeros([n.value] + ([2] if self.is_complex else []), dtype=NP_SCALAR[self.scalar])
+        _lib.check(get(self._h, _np_ptr(a), n.value, C.byref(n)))
+        return a
+
+    def _stream(self, x, what):
+        x = np.ascontiguousarray(as_pairs(x))
+        want = 2 if self.is_complex else 1
+        if x.dtype != NP_SCALAR[self.scalar] or x.ndim != want or (self.is_complex and x.shape[1] != 2):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "%s: %s%s for a %s%s stream" % (what, x.dtype, x.shape, "complex " if self.is_complex else "",
+                                                                                       np.dtype(NP_SCALAR[self.scalar]).name))
+        return x
+
+
+class SymbolMapper(_SymbolMap):
+    """pcx_mapper_*: digital/SymbolMapper.cpp's loop, out[i] = map[in[i] & mask].  uint8 in, the stream type out."""
+    _destroy = "pcx_mapper_destroy"
+    _family = "pcx_mapper"
+
+    def process(self, x):
+        x = np.ascontiguousarray(x)
+        if x.dtype != np.uint8 or x.ndim != 1:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "symbol mapper: %s%s input for a uint8 block" % (x.dtype, x.shape))
+        y = np.zeros([x.shape[0]] + ([2] if self.is_complex else []), dtype=NP_SCALAR[self.scalar])
+        _lib.check(_lib.load().pcx_mapper_process(self._h, _np_ptr(x), _np_ptr(y), x.shape[0]))
+        return y
+
+    def process_dev(self, x, y, n, stream=None):
+        _lib.check(_lib.load().pcx_mapper_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
+
+
+class SymbolSlicer(_SymbolMap):
+    """pcx_slicer_*: digital/SymbolSlicer.cpp's loop -- the first map entry with the strictly smallest float distance, as a byte
+    (DESIGN.md 14).  The stream type in, uint8 out."""
+    _destroy = "pcx_slicer_destroy"
+    _family = "pcx_slicer"
+
+    def geometry(self):
+        """(lane, group, max_onchip_map, slice): samples a lane and a workgroup hold, the longest map held on chip, elements per call slice"""
+        v = [C.c_size_t() for _ in range(4)]
+        _lib.check(_lib.load().pcx_slicer_get_geometry(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def process(self, x):
+        x = self._stream(x, "symbol slicer")
+        y = np.zeros(x.shape[0], dtype=np.uint8)
+        _lib.check(_lib.load().pcx_slicer_process(self._h, _np_ptr(x), _np_ptr(y), x.shape[0]))
+        return y
+
+    def process_dev(self, x, y, n, stream=None):
+        _lib.check(_lib.load().pcx_slicer_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
+
+
+class DifferentialCoder(_Handle):
+    """pcx_diffcode_*: digital/DifferentialEncoder.cpp's and DifferentialDecoder.cpp's loops, byte for byte.  One uint8
+    per symbol in and out; the carried byte survives calls and set_symbols.
+
+    plan() says how the handle computes: DIFF_SCAN when the encoder's step is a modular prefix sum for this symbols (checked over all
+    65536 byte pairs), DIFF_SERIAL (one thread, the reference's loop) otherwise; the decoder always reports DIFF_SCAN."""
+    _destroy = "pcx_diffcode_destroy"
+
+    def __init__(self, decode=False, symbols=2):
+        super().__init__()
+        self.decode = bool(decode)
+        _lib.check(_lib.load().pcx_diffcode_create(int(self.decode), C.byref(self._h)))
+        if symbols != 2:
+            self.set_symbols(symbols)
+
+    def set_symbols(self, symbols):
+        symbols = int(symbols)
+        if not 0 <= symbols < 1 << 32:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "symbols is a uint32_t: %d" % symbols)
+        _lib.check(_lib.load().pcx_diffcode_set_symbols(self._h, symbols))
+
+    def symbols(self):
+        v = C.c_uint32()
+        _lib.check(_lib.load().pcx_diffcode_get_symbols(self._h, C.byref(v)))
+        return v.value
+
+    def plan(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_diffcode_get_plan(self._h, C.byref(v)))
+        return v.value
+
+    def state(self):
+        """the carried byte after the handle's last call"""
+        v = C.c_ubyte()
+        _lib.check(_lib.load().pcx_diffcode_get_state(self._h, C.byref(v)))
+        return v.value
+
+    def reset(self):
+        _lib.check(_lib.load().pcx_diffcode_reset(self._h))
+
+    @staticmethod
+    def geometry():
+        """(tile, slice): the bytes a workgroup and a call slice hold"""
+        t, s = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.load().pcx_diffcode_get_geometry(C.byref(t), C.byref(s)))
+        return t.value, s.value
+
+    def process(self, x, out=None):
+        """x: (n,) uint8; returns the n output bytes (out=x works in place)"""
+        x = np.ascontiguousarray(x)
+        if x.dtype != np.uint8 or x.ndim != 1:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "differential coder: %s%s input for a uint8 block" % (x.dtype, x.shape))
+        if out is None:
+            y = np.zeros_like(x)
+        else:
+            y = out
+            if not (isinstance(y, np.ndarray) and y.dtype == x.dtype and y.shape == x.shape and y.flags.c_contiguous):
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "differential coder: out must be a contiguous uint8 array of shape %s" % (x.shape,))
+        _lib.check(_lib.load().pcx_diffcode_process(self._h, _np_ptr(x), _np_ptr(y), x.shape[0]))
+        return y
+
+    def process_dev(self, x, y, n, stream=None):
+        _lib.check(_lib.load().pcx_diffcode_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
