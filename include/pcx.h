@@ -540,6 +540,50 @@ PCX_API int pcx_diffcode_process(pcx_diffcode *h, const void *in, void *out, siz
 PCX_API int pcx_diffcode_process_dev(pcx_diffcode *h, const void *in_dev, void *out_dev, size_t n, void *stream);
 
 /* ===================================================================== *
+ *  /comms/bits_to_symbols, /comms/symbols_to_bits, /comms/bytes_to_symbols, /comms/symbols_to_bytes   (digital/)
+ *
+ *  The four conversions of digital/SymbolHelpers.hpp between bits (one per byte), symbols of `modulus` = 1 ... 8 bits (one per byte)
+ *  and payload bytes, in MSBit or LSBit order.  uint8 in, uint8 out, no state between calls.  Every output byte equals the
+ *  reference's loop for all 256 values of every input byte:
+ *    bits -> symbols   (:13-41)    an input byte counts as 1 when it is not 0
+ *    symbols -> bits   (:46-72)    only the low `modulus` bits of a symbol are looked at; outputs are 0 or 1
+ *    bytes -> symbols  (:233-414)  outputs are below 2^modulus
+ *    symbols -> bytes  (:77-228)   the reference ORs shifted symbols it never masks: the whole 8-bit value of a symbol is placed with
+ *                                  its bit 0 on its field's lowest bit and cut off at the upper edge of the last byte the field
+ *                                  touches, so bits above the width land on the fields above it
+ *  DEVIATION: the packet path of the four blocks (msgWork, e.g. BytesToSymbols.cpp:91-119) has no counterpart here: it rounds a
+ *  packet up to whole groups and reads past the payload's end to do so, which is undefined.
+ * ===================================================================== */
+typedef struct pcx_repack pcx_repack;
+enum { PCX_REPACK_BITS_TO_SYMBOLS = 0, PCX_REPACK_SYMBOLS_TO_BITS = 1,
+       PCX_REPACK_BYTES_TO_SYMBOLS = 2, PCX_REPACK_SYMBOLS_TO_BYTES = 3 };
+/* The constructors' values, not the descriptions' defaults: modulus 1 for all four, MSBit for the two bit kinds
+ * (BitsToSymbols.cpp:49, SymbolsToBits.cpp:46), LSBit for the two byte kinds (BytesToSymbols.cpp:43-46, SymbolsToBytes.cpp:46-49).
+ * Checked in this order: out, then the kind (unknown: PCX_ERR_ARG). */
+PCX_API int pcx_repack_create(int kind, pcx_repack **out);
+PCX_API int pcx_repack_destroy(pcx_repack *h);
+/* setModulus (:64-71 of BitsToSymbols.cpp, the same in the other three): outside 1 ... 8 is PCX_ERR_ARG
+ * "Modulus must be between 1 and 8 inclusive", checked after the handle; the previous value is kept. */
+PCX_API int pcx_repack_set_modulus(pcx_repack *h, unsigned mod);
+PCX_API int pcx_repack_get_modulus(const pcx_repack *h, unsigned *mod);
+/* setBitOrder (:78-83): msb != 0 is "MSBit", 0 is "LSBit" (the blocks map the strings and refuse any other with "Order must be
+ * LSBit or MSBit") */
+PCX_API int pcx_repack_set_bit_order(pcx_repack *h, int msb);
+PCX_API int pcx_repack_get_bit_order(const pcx_repack *h, int *msb);
+/* the indivisible unit the reference reserves, in input and output elements: bits -> symbols (w, 1), symbols -> bits (1, w),
+ * bytes -> symbols _reserveBytes = 1, 1, 3, 1, 5, 3, 7, 1 at w = 1 ... 8 (BytesToSymbols.cpp:69-76) and the 8 in / w symbols they
+ * hold, symbols -> bytes _reserveSyms = 8, 4, 8, 2, 8, 4, 8, 1 (SymbolsToBytes.cpp:72-79) and their in w / 8 bytes */
+PCX_API int pcx_repack_get_group(const pcx_repack *h, size_t *in_elems, size_t *out_elems);
+/* input elements a workgroup and a call slice hold at the handle's setting (the seams a test wants to straddle) */
+PCX_API int pcx_repack_get_geometry(const pcx_repack *h, size_t *tile, size_t *slice);
+/* n counts INPUT elements; the output holds n / in_group * out_group elements.  Checked in this order before any device call: the
+ * handle, n == 0 (nothing to do: PCX_OK), n not a whole number of groups (PCX_ERR_ARG "not a whole group"), null buffers, any
+ * overlap of the input bytes with the output bytes.  process_dev synchronises nothing and allocates nothing: it can be captured
+ * into a graph.  n is a size_t and every index in the kernels is 64-bit. */
+PCX_API int pcx_repack_process(pcx_repack *h, const void *in, void *out, size_t n);
+PCX_API int pcx_repack_process_dev(pcx_repack *h, const void *in_dev, void *out_dev, size_t n, void *stream);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

@@ -22,6 +22,7 @@ SCR_ADDITIVE, SCR_MULTIPLICATIVE = 0, 1     # pcx_scrambler_set_mode
 SCR_SCAN, SCR_SERIAL = 0, 1          # pcx_scrambler_get_plan
 PRE_PLANES, PRE_BYTES = 0, 1         # pcx_preamble_get_plan
 DIFF_SCAN, DIFF_SERIAL = 0, 1        # pcx_diffcode_get_plan
+REPACK_BITS_TO_SYMBOLS, REPACK_SYMBOLS_TO_BITS, REPACK_BYTES_TO_SYMBOLS, REPACK_SYMBOLS_TO_BYTES = 0, 1, 2, 3      # pcx_repack_create
 
 
 class PcxError(RuntimeError):
@@ -189,6 +190,16 @@ SIGNATURES = {
     "pcx_diffcode_reset": (_i, [_vp]),
     "pcx_diffcode_process": (_i, [_vp, _vp, _vp, _sz]),
     "pcx_diffcode_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_repack_create": (_i, [_i, C.POINTER(_vp)]),
+    "pcx_repack_destroy": (_i, [_vp]),
+    "pcx_repack_set_modulus": (_i, [_vp, C.c_uint]),
+    "pcx_repack_get_modulus": (_i, [_vp, C.POINTER(C.c_uint)]),
+    "pcx_repack_set_bit_order": (_i, [_vp, _i]),
+    "pcx_repack_get_bit_order": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_repack_get_group": (_i, [_vp, _psz, _psz]),
+    "pcx_repack_get_geometry": (_i, [_vp, _psz, _psz]),
+    "pcx_repack_process": (_i, [_vp, _vp, _vp, _sz]),
+    "pcx_repack_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

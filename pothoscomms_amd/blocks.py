@@ -32,11 +32,12 @@ _blib = None
 # libpcx_iir_blocks.so (iir_blocks.cpp: /comms/iir_filter), "digital" libpcx_digital_blocks.so (digital_blocks.cpp: /comms/scrambler,
 # /comms/descrambler), "correlator" libpcx_correlator_blocks.so (correlator_blocks.cpp: /comms/preamble_correlator), "symbol"
 # libpcx_symbol_blocks.so (symbol_blocks.cpp: /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder,
-# /comms/differential_decoder) -- one registry each, as Pothos loads one module library per source directory
+# /comms/differential_decoder), "repack" libpcx_repack_blocks.so (repack_blocks.cpp: /comms/bits_to_symbols, /comms/symbols_to_bits,
+# /comms/bytes_to_symbols, /comms/symbols_to_bytes) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
-           "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so")}
+           "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so")}
 _mlibs = {}
 
 
@@ -257,7 +258,7 @@ class Block:
             return [int(b) for b in buf[:cnt.value]]
         if not args:   # getter
             if name in ("getThreshold", "getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
-                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols"):
+                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value

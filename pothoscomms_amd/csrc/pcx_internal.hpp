@@ -319,6 +319,12 @@ int launch_sym_map(int scalar, bool cplx, const void *in, void *out, size_t m, c
 int launch_sym_slice(int scalar, bool cplx, const void *in, void *out, size_t m, const void *mapc, size_t M, hipStream_t st);
 // one slice of m bytes; state[0]: the carried byte, in and out; tsum, tin: one word per tile of a slice
 int launch_diff_slice(const DiffShape &p, const void *in, void *out, size_t m, uint32_t *state, uint32_t *tsum, uint32_t *tin, hipStream_t st);
+// (repack.hip) /comms/bits_to_symbols, /comms/symbols_to_bits, /comms/bytes_to_symbols, /comms/symbols_to_bytes
+size_t repack_tile(int kind, unsigned w);                           // input elements per workgroup and per call slice (whole tiles)
+size_t repack_slice(int kind, unsigned w);
+size_t repack_out_elems(int kind, unsigned w, size_t in_elems);     // of a whole number of groups
+// one slice of m input elements, a whole number of groups
+int launch_repack_slice(int kind, unsigned w, bool msb, const void *in, void *out, size_t m, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

@@ -759,6 +759,80 @@ class DifferentialCoder(_Handle):
         _lib.check(_lib.load().pcx_diffcode_process_dev(self._h, _dev_ptr(x), _dev_ptr(y), n, _stream_ptr(stream)))
 
 
+REPACK_KINDS = {"bits_to_symbols": _lib.REPACK_BITS_TO_SYMBOLS, "symbols_to_bits": _lib.REPACK_SYMBOLS_TO_BITS,
+                "bytes_to_symbols": _lib.REPACK_BYTES_TO_SYMBOLS, "symbols_to_bytes": _lib.REPACK_SYMBOLS_TO_BYTES}
+
+
+class SymbolRepacker(_Handle):
+    """pcx_repack_*: the four conversions of digital/SymbolHelpers.hpp between bits (one per byte), symbols of `modulus` bits (one per
+    byte) and payload bytes, byte for byte.  uint8 in and out, nothing carried between calls.
+
+    A fresh handle holds the reference's constructor values: modulus 1, "MSBit" for the two bit kinds, "LSBit" for the two byte
+    kinds.  A call takes a whole number of group()[0] input elements and gives group()[1] outputs for each."""
+    _destroy = "pcx_repack_destroy"
+
+    def __init__(self, kind, modulus=None, bit_order=None):
+        super().__init__()
+        if kind not in REPACK_KINDS:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "repack: unknown kind %r (%s)" % (kind, ", ".join(sorted(REPACK_KINDS))))
+        self.kind = kind
+        _lib.check(_lib.load().pcx_repack_create(REPACK_KINDS[kind], C.byref(self._h)))
+        if modulus is not None:
+            self.set_modulus(modulus)
+        if bit_order is not None:
+            self.set_bit_order(bit_order)
+
+    def set_modulus(self, modulus):
+        modulus = int(modulus)
+        _lib.check(_lib.load().pcx_repack_set_modulus(self._h, modulus if 0 <= modulus < 1 << 32 else 0))
+
+    def modulus(self):
+        v = C.c_uint()
+        _lib.check(_lib.load().pcx_repack_get_modulus(self._h, C.byref(v)))
+        return v.value
+
+    def set_bit_order(self, order):
+        if order not in ("LSBit", "MSBit"):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "Order must be LSBit or MSBit")
+        _lib.check(_lib.load().pcx_repack_set_bit_order(self._h, int(order == "MSBit")))
+
+    def bit_order(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_repack_get_bit_order(self._h, C.byref(v)))
+        return "MSBit" if v.value else "LSBit"
+
+    def group(self):
+        """(in, out): the indivisible unit the reference reserves, in input and output elements"""
+        a, b = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.load().pcx_repack_get_group(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def geometry(self):
+        """(tile, slice): the input elements a workgroup and a call slice hold at the handle's setting"""
+        t, s = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.load().pcx_repack_get_geometry(self._h, C.byref(t), C.byref(s)))
+        return t.value, s.value
+
+    def out_elems(self, n):
+        gin, gout = self.group()
+        return n // gin * gout
+
+    def process(self, x):
+        """x: (n,) uint8, a whole number of groups; returns the n / group()[0] * group()[1] output bytes"""
+        x = np.ascontiguousarray(x)
+        if x.dtype != np.uint8 or x.ndim != 1:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "repack: %s%s input for a uint8 block" % (x.dtype, x.shape))
+        y = np.zeros(self.out_elems(x.shape[0]), np.uint8)
+        _lib.check(_lib.load().pcx_repack_process(self._h, _np_ptr(x), _np_ptr(y), x.shape[0]))
+        return y
+
+    def process_dev(self, x, out, n, stream=None):
+        """x, out: CUDA/ROCm uint8 tensors or raw device addresses; n input elements"""
+        ptr = lambda t: C.c_void_p(t) if isinstance(t, int) else _dev_ptr(t)      # noqa: E731
+        _lib.check(_lib.load().pcx_repack_process_dev(self._h, ptr(x), ptr(out), n, _stream_ptr(stream)))
+        return out
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
