@@ -382,8 +382,10 @@ PCX_API int pcx_iir_reset(pcx_iir *h);
  * recurrence's value (0 for SERIAL, which is that recurrence bit for bit) */
 PCX_API int pcx_iir_get_plan(const pcx_iir *h, int *plan, double *bound);
 /* work()'s loop (IIRFilter.cpp:82-99) over n elements, the history carried across calls: y = sum b_k x[n-k] - sum a_k y[n-k] in
- * double, narrowed to the stream type (float32 to nearest; integers toward zero, saturated, NaN -> 0).  process_dev synchronises
- * nothing and allocates nothing: it can be captured into a graph. */
+ * double, narrowed to the stream type (float32 to nearest; integers toward zero, saturated, NaN -> 0).  Checked in this order before
+ * any device call: the handle, n == 0 (nothing to do), null buffers, any overlap of the n input elements with the n output elements
+ * (PCX_ERR_ARG, out == in included: the kernels read a slice's inputs again after outputs have been written).  process_dev
+ * synchronises nothing and allocates nothing: it can be captured into a graph. */
 PCX_API int pcx_iir_process(pcx_iir *h, const void *in, void *out, size_t n);
 PCX_API int pcx_iir_process_dev(pcx_iir *h, const void *in_dev, void *out_dev, size_t n, void *stream);
 

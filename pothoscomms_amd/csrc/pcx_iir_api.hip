@@ -82,6 +82,13 @@ struct pcx_iir {
     StageBuf wsIn, wsOut;
 };
 
+// the apply and finish kernels read a slice's inputs after outputs have been written: no byte of the two buffers may be shared
+static bool iir_disjoint(const void *in, const void *out, size_t bytes)
+{
+    const char *a = static_cast<const char *>(in), *b = static_cast<const char *>(out);
+    return a + bytes <= b || b + bytes <= a;
+}
+
 static int iir_zero_state(pcx_iir *h, hipStream_t st)
 {
     PCX_TRY(launch_zero_words(h->xh.p, h->xh.cap / 4, st));
@@ -261,9 +268,10 @@ int pcx_iir_process_dev(pcx_iir *h, const void *in_dev, void *out_dev, size_t n,
 {
     PCX_TRACE();
     PCX_CHECK_ARG(h, "null handle");
-    DeviceScope dev_scope(h->cx.device);
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    PCX_CHECK_ARG(iir_disjoint(in_dev, out_dev, n * h->elem), "iir_filter: out overlaps in (out == in included)");
+    DeviceScope dev_scope(h->cx.device);
     hipStream_t st = as_stream(stream);
     PCX_TRY(ctx_enter(h->cx, st));
     const char *in = static_cast<const char *>(in_dev);
@@ -281,10 +289,11 @@ int pcx_iir_process(pcx_iir *h, const void *in, void *out, size_t n)
 {
     PCX_TRACE();
     PCX_CHECK_ARG(h, "null handle");
-    DeviceScope dev_scope(h->cx.device);
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t bytes = n * h->elem;
+    PCX_CHECK_ARG(iir_disjoint(in, out, bytes), "iir_filter: out overlaps in (out == in included)");
+    DeviceScope dev_scope(h->cx.device);
     hipStream_t st;
     PCX_TRY(ctx_own_stream(h->cx, &st));
     const void *din; void *dout; bool staged;

@@ -219,6 +219,50 @@ def named_set():
             "butter6_0.2": taps_of(butter(6, 0.4)), "cheby1_4_0.1dB_0.2": taps_of(cheby1(4, 0.1, 0.4))}
 
 
+# ---- orders 9 to 32: the SCAN buckets NB = 16 and 32, and every one of the 32 carried history slots
+SPREAD_ORDERS = (9, 12, 16, 17, 24, 31, 32)
+COMBS = ((9, 0.5), (16, -0.5), (17, -0.9), (31, 0.5), (32, -0.5))
+UNSTABLE_ORDERS = (3, 9, 16, 17, 31, 32)
+
+
+def _draw(seed, N):
+    """(pole-pair angles, b of l1 norm 1 and every |b_k| >= 0.01) of order N, drawn in this order"""
+    rng = np.random.default_rng(seed)
+    k = N // 2
+    ang = (np.arange(k) + 0.5 + rng.uniform(-0.2, 0.2, k)) * np.pi / k
+    b = rng.uniform(0.2, 1, N + 1) * rng.choice([-1, 1], N + 1)
+    return ang, b / np.abs(b).sum()
+
+
+def spread(N, last_radius=None):
+    """order N with its pole pairs spread over the upper half circle at radii 0.7 ... 0.9 (a real pole at 0.5 for an odd N) and
+    every feedforward tap of weight; last_radius moves the last pair"""
+    ang, b = _draw(N, N)
+    k = N // 2
+    rad = np.linspace(0.7, 0.9, k)
+    if last_radius is not None:
+        rad[-1] = last_radius
+    p = rad * np.exp(1j * ang)
+    poles = np.concatenate([p, np.conj(p), [0.5] if N % 2 else []])
+    a = np.real(np.poly(poles))
+    return list(np.concatenate([b, a]))
+
+
+def comb(N, g):
+    """a = 1 + g z^-N: the whole feedback on the oldest history slot of the order (b drawn behind the angles, as spread's is)"""
+    a = np.zeros(N + 1)
+    a[0], a[N] = 1.0, g
+    return list(np.concatenate([_draw(100 + N, N)[1], a]))
+
+
+def high_order_set():
+    """spreadN and combN plan as SCAN with a bound below 1e-10, unstableN (a pole pair at radius 1.004) as SERIAL"""
+    s = {"spread%d" % N: spread(N) for N in SPREAD_ORDERS}
+    s.update({"comb%d" % N: comb(N, g) for N, g in COMBS})
+    s.update({"unstable%d" % N: spread(N, 1.004) for N in UNSTABLE_ORDERS})
+    return s
+
+
 # ---- the residual check (numpy or torch float64 arrays)
 def residual_check(x, y, taps, name, bound, xmax=None, skip=0):
     """first index n >= skip (-1: none) where r[n] = y[n] + sum a_k y[n-k] - sum b_k x[n-k] leaves its tolerance.  x, y: float64 arrays of

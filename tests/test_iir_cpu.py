@@ -2,6 +2,7 @@
 bound restated, the residual check, the C ABI's argument checks, the registry of libpcx_iir_blocks.so and the block's description."""
 import ctypes as C
 import os
+import re
 import shutil
 import subprocess
 
@@ -70,6 +71,50 @@ def test_named_set_plans_scan_within_1e_10_and_unstable_filters_serial():
         assert M.plan(taps) == ("SERIAL", 0.0), taps
     assert M.schur_cohn([1, -0.5]) == [-0.5]
     assert M.plan([2, 1])[0] == "SCAN"
+
+
+def test_high_order_set_meets_the_conditions_its_gpu_tests_rest_on():
+    """what keeps a tolerance of the GPU tests from hiding a fault: a bound below 1e-10 on every SCAN filter, no feedforward tap
+    below 0.01 (of an l1 norm of 1), no feedback tap of a spread filter below 1e-5 (dropping any one tap moves a float64 output by
+    far more than bound * max|x|), all the feedback of a comb on its oldest slot; the unstable filters SERIAL and within 1e7 over
+    the 3000 samples they are run on, so that every output and every slot of the history still counts in double"""
+    hs = M.high_order_set()
+    assert sorted(hs) == sorted(["spread%d" % n for n in (9, 12, 16, 17, 24, 31, 32)] + ["comb%d" % n for n in (9, 16, 17, 31, 32)]
+                                + ["unstable%d" % n for n in (3, 9, 16, 17, 31, 32)])
+    x = np.random.default_rng(7).uniform(-1, 1, 3000)
+    for name, taps in hs.items():
+        N = int(re.search(r"\d+$", name).group())
+        b, a = M.normalise(taps)
+        assert len(taps) == 2 * (N + 1) and a[0] == 1.0, name
+        assert np.min(np.abs(b)) >= 0.01 and abs(np.abs(b).sum() - 1) < 1e-12, (name, np.min(np.abs(b)))
+        plan, bound = M.plan(taps)
+        if name.startswith("unstable"):
+            assert (plan, bound) == ("SERIAL", 0.0), name
+            yd, _ = M.run(x, taps, "float64")
+            assert np.all(np.isfinite(yd)) and 1e3 < np.max(np.abs(yd)) < 1e7, (name, np.max(np.abs(yd)))
+            continue
+        assert plan == "SCAN" and 0 < bound <= 1e-10, (name, plan, bound)
+        if name.startswith("spread"):
+            assert np.min(np.abs(a)) >= 1e-5, (name, np.min(np.abs(a)))
+        else:
+            assert np.count_nonzero(a) == 2 and abs(a[N]) >= 0.5, name
+
+
+def test_high_order_model_against_scipy_and_across_short_calls():
+    ss = pytest.importorskip("scipy.signal")
+    x = np.random.default_rng(8).uniform(-1, 1, (600, 2))
+    cuts = [1, 1, 2, 5, 16, 7, 31, 32, 33, 64, 408]
+    for name, taps in M.high_order_set().items():
+        if name.startswith("unstable"):
+            continue
+        b, a = M.normalise(taps)
+        whole = M.Model(taps, True).process_double(x)
+        assert np.max(np.abs(whole - ss.lfilter(b, a, x, axis=0))) <= M.plan(taps)[1], name
+        m, pos, parts = M.Model(taps, True), 0, []
+        for c in cuts:
+            parts.append(m.process_double(x[pos:pos + c]))
+            pos += c
+        assert pos == 600 and np.array_equal(whole, np.concatenate(parts)), name
 
 
 def test_narrowing():

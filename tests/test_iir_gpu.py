@@ -14,7 +14,38 @@ pytestmark = pytest.mark.gpu
 
 TYPES = list(M.SCALARS)
 DTYPES = TYPES + ["complex_" + t for t in TYPES]
-CUTS = [1, 37, 100, 11, 251, 4096, 3500, 2004]       # 10000 samples, four tiles
+CUTS = [1, 37, 100, 11, 251, 4096, 3500, 2004]       # 10000 samples: three tiles as one call, the last one partial
+# orders 9 to 32 (the buckets NB = 16 and 32).  These cuts reach every one of the 32 carried history slots: several calls in a row
+# shorter than the order (finish shifts the old history by 1, 1, 2, 5, 16, 7 and 31), calls of 31, 32 and 33, one that ends on the
+# call's tile (4096) with a single sample behind it, and a last call of 1808
+HIGH = M.high_order_set()
+HIGH_SCAN = [k for k in HIGH if not k.startswith("unstable")]
+HIGH_N = 10000
+HIGH_CUTS = [1, 1, 2, 5, 16, 7, 31, 32, 33, 64, 4095 - 192, 4096, 1]
+HIGH_CUTS.append(HIGH_N - sum(HIGH_CUTS))
+_PLANS = {}
+
+
+def model_bound(fname):
+    if fname not in _PLANS:
+        _PLANS[fname] = M.plan(HIGH[fname])
+    assert _PLANS[fname][0] == "SCAN"
+    return _PLANS[fname][1]
+
+
+def scan_handle(h, fname):
+    """h retuned to the filter fname of the high-order set; the handle's bound, which must be the model's and below 1e-10 (a
+    handle that reported a large bound would pass anything)"""
+    from pothoscomms_amd import _lib
+    h.set_taps(HIGH[fname])
+    plan, bound = h.plan()
+    assert plan == _lib.IIR_SCAN and 0 < bound <= 1e-10, (fname, plan, bound)
+    assert abs(bound - model_bound(fname)) <= 1e-6 * bound, (fname, bound, model_bound(fname))
+    return bound
+
+
+def xmax(x):
+    return float(np.max(np.abs(x.astype(np.float64))))
 
 
 def _torch_of(x):
@@ -286,3 +317,176 @@ def test_beyond_2_31_elements(dev):
         xs, ys = x[lo:b0].to(torch.float64), y[lo:b0].to(torch.float64)
         assert M.residual_check(xs, ys, taps, "int8", bound, xmax=16.0, skip=a0 - lo) == -1, a0
         del xs, ys
+
+
+# ---- orders 9 to 32
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_high_order_buckets_within_the_bound_cut_whole_and_device(dev, dtype):
+    """every type on NB = 16 and 32: one handle retuned 16 -> 16 -> 32 -> 32 -> 16 -> 32, each stream in HIGH_CUTS, whole, and
+    through process_dev"""
+    import torch
+    name, cplx = M.split(dtype)
+    assert sum(HIGH_CUTS) == HIGH_N and HIGH_CUTS[-1] > 0
+    h = dev.IIRFilter(dtype)
+    for fname in ("spread9", "spread16", "spread17", "spread32", "comb16", "comb32"):
+        bound = scan_handle(h, fname)
+        for kind in ("noise", "full"):
+            x = stream(dtype, HIGH_N, kind, zlib.crc32(("%s/%s/%s" % (dtype, fname, kind)).encode()))
+            yd, _ = M.run(x, HIGH[fname], name)
+            tol = bound * xmax(x)
+            h.reset()
+            cut = feed(h, x, HIGH_CUTS)
+            assert within(cut, yd, tol, name), (dtype, fname, kind, "cut")
+            h.reset()
+            whole = h.process(x)
+            assert within(whole, yd, tol, name), (dtype, fname, kind, "whole")
+            h.reset()
+            yt = torch.empty_like(_torch_of(x))
+            h.process_dev(_torch_of(x), yt, HIGH_N)
+            assert np.array_equal(yt.cpu().numpy(), whole, equal_nan=name.startswith("float")), (dtype, fname, kind, "dev")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "complex_int16"])
+def test_every_high_order_scan_filter_in_cuts(dev, dtype):
+    """the orders between the buckets' ends as well (12, 24, 31) and every comb"""
+    name, cplx = M.split(dtype)
+    h = dev.IIRFilter(dtype)
+    for fname in HIGH_SCAN:
+        bound = scan_handle(h, fname)
+        x = stream(dtype, HIGH_N, "noise", zlib.crc32(fname.encode()))
+        yd, _ = M.run(x, HIGH[fname], name)
+        assert within(feed(h, x, HIGH_CUTS), yd, bound * xmax(x), name), (dtype, fname)
+
+
+def test_comb32_impulse_is_exactly_half_to_the_j_every_32_samples_on_scan(dev):
+    """a = 1 - 0.5 z^-32, b = 1: every entry of every table is 0 or a power of two, every sum has one term that is not zero"""
+    from pothoscomms_amd import _lib
+    taps = [1.0] + [0.0] * 32 + [1.0] + [0.0] * 31 + [-0.5]
+    h = dev.IIRFilter("float64", taps)
+    assert h.plan()[0] == _lib.IIR_SCAN
+    x = np.zeros(9000)
+    x[0] = 1.0
+    want = np.zeros(9000)
+    want[::32] = np.ldexp(1.0, -np.arange(len(want[::32])))
+    assert np.array_equal(h.process(x), want)
+    h.reset()
+    assert np.array_equal(feed(h, x, [1, 31, 1, 4063, 4904]), want)
+
+
+@pytest.mark.parametrize("fname", ["spread17", "comb32"])
+@pytest.mark.parametrize("dtype", ["float64", "complex_int16"])
+def test_carry_second_level_against_the_model(dev, dtype, fname):
+    """66 tiles in one call: the carry kernel's scan over runs of 64 tiles hands thread 1 its incoming state; and the same stream cut
+    three samples in front of the 64th tile's end"""
+    name, cplx = M.split(dtype)
+    n = 65 * 4096 + 7
+    h = dev.IIRFilter(dtype)
+    bound = scan_handle(h, fname)
+    x = stream(dtype, n, "noise", zlib.crc32(("carry/%s/%s" % (dtype, fname)).encode()))
+    yd, _ = M.run(x, HIGH[fname], name)
+    tol = bound * xmax(x)
+    assert within(h.process(x), yd, tol, name), "whole"
+    h.reset()
+    assert within(feed(h, x, [64 * 4096 - 3, 4096 + 10]), yd, tol, name), "cut"
+
+
+@pytest.mark.parametrize("fname", ["spread32", "comb32"])
+@pytest.mark.parametrize("dtype", ["complex_float32", "float64"])
+def test_high_order_1mi_samples_by_the_residual_on_the_device(dev, dtype, fname):
+    import torch
+    name, cplx = M.split(dtype)
+    n = 1 << 20
+    h = dev.IIRFilter(dtype)
+    bound = scan_handle(h, fname)
+    g = torch.Generator(device="cuda:0").manual_seed(14)
+    x = torch.rand((n, 2) if cplx else (n,), device="cuda:0", generator=g, dtype=getattr(torch, name)) * 2 - 1
+    y = torch.empty_like(x)
+    h.process_dev(x, y, n)
+    assert M.residual_check(x.to(torch.float64), y.to(torch.float64), HIGH[fname], name, bound) == -1
+
+
+@pytest.mark.parametrize("dtype", ["float64", "complex_float32", "int8", "int64", "complex_int16"])
+def test_high_order_unstable_filters_are_serial_and_bit_exact(dev, dtype):
+    """the SERIAL loop and its rings at orders 3 to 32, the history carried over calls shorter than, equal to and longer than the
+    order and the ring"""
+    from pothoscomms_amd import _lib
+    name, cplx = M.split(dtype)
+    cuts = [1, 2, 5, 31, 32, 33, 63, 64, 65]
+    cuts.append(3000 - sum(cuts))
+    h = dev.IIRFilter(dtype)
+    for fname in HIGH:
+        if not fname.startswith("unstable"):
+            continue
+        h.set_taps(HIGH[fname])
+        assert h.plan() == (_lib.IIR_SERIAL, 0.0), fname
+        x = stream(dtype, 3000, "noise", zlib.crc32(fname.encode()))
+        _, want = M.run(x, HIGH[fname], name)
+        assert same(feed(h, x, cuts), want), (dtype, fname)
+
+
+@pytest.mark.parametrize("dtype", ["int8", "complex_float64"])
+def test_high_order_odd_lengths_leave_the_guard_bands_alone(dev, dtype):
+    import torch
+    name, cplx = M.split(dtype)
+    guard = 4096
+    h = dev.IIRFilter(dtype)
+    bound = scan_handle(h, "spread32")
+    for n in (1, 31, 4095, 4096, 4097):
+        x = stream(dtype, n, "noise", 40 + n)
+        yd, _ = M.run(x, HIGH["spread32"], name)
+        for off in (1, 3):
+            total = guard + off + n + guard
+            raw = torch.full((total * x.itemsize * (2 if cplx else 1),), 0xA5, dtype=torch.uint8, device="cuda:0")
+            buf = raw.view(getattr(torch, name)).reshape((total, 2) if cplx else (total,))
+            h.reset()
+            h.process_dev(_torch_of(x), buf[guard + off:guard + off + n], n)
+            got = buf.cpu().numpy()
+            lo, hi = got[:guard + off], got[guard + off + n:]
+            assert np.all(lo.view(np.uint8) == 0xA5) and np.all(hi.view(np.uint8) == 0xA5), (dtype, n, off)
+            assert within(got[guard + off:guard + off + n], yd, bound * xmax(x), name), (dtype, n, off)
+
+
+def test_block_with_the_66_taps_of_order_32(dev):
+    from pothoscomms_amd import blocks as B
+    taps = HIGH["spread32"]
+    assert len(taps) == 66
+    x = stream("complex_float32", 10000, "noise", 31)
+    blk = B.make("/comms/iir_filter", "complex_float32", module="iir")
+    blk.call("setTaps", taps)
+    assert np.array_equal(blk.call("getTaps"), taps)
+    blk.activate()
+    y, consumed, produced, _, _ = blk.work(x, 10000)
+    assert consumed == produced == 10000
+    assert np.array_equal(y[:produced], dev.IIRFilter("complex_float32", taps).process(x))
+
+
+def test_overlapping_buffers_are_refused_and_the_handle_stays_good(dev):
+    """the apply kernel reads a tile's halo and the finish kernel the last inputs after outputs have been written: any overlap of
+    the n input with the n output elements is refused before the device is touched, out == in included"""
+    import torch
+    from pothoscomms_amd import _lib
+    taps = HIGH["spread32"]
+    x = stream("complex_float32", 10000, "noise", 32)
+    f = dev.IIRFilter("complex_float32", taps)
+    fresh = [f.process(x[:100]), f.process(x[100:])]
+    h = dev.IIRFilter("complex_float32", taps)
+    assert np.array_equal(h.process(x[:100]), fresh[0])       # a history that a refused call must leave alone
+    xd = _torch_of(x)
+    for a, b in ((xd, xd), (xd[:1000], xd[1:1001]), (xd[8:1008], xd[:1000]), (xd[:5000], xd[4999:9999])):
+        with pytest.raises(_lib.InvalidArgument, match="overlaps"):
+            h.process_dev(a, b, a.shape[0])
+    xh = x.copy()
+    for a, b in ((xh, xh), (xh[:1000], xh[1:1001]), (xh[999:1999], xh[:1000])):
+        with pytest.raises(_lib.InvalidArgument, match="overlaps"):
+            h.process(a, out=b)
+    torch.cuda.synchronize()
+    assert np.array_equal(xd.cpu().numpy(), x) and np.array_equal(xh, x)
+    assert np.array_equal(h.process(x[100:]), fresh[1])
+    # buffers that touch without overlapping are accepted
+    f.reset()
+    want = np.concatenate([f.process(x[:5000]), f.process(x[5000:])])
+    h.reset()
+    yd = torch.empty_like(xd)
+    h.process_dev(xd[:5000], yd[:5000], 5000)
+    h.process_dev(xd[5000:], xd[:5000], 5000)
+    assert np.array_equal(torch.cat([yd[:5000], xd[:5000]]).cpu().numpy(), want)
