@@ -20,7 +20,7 @@ using pcxfw::InvalidArgumentException;
 
 namespace {
 
-using namespace pcxblk;     // check, OnDevice, kDomain, the port-slab bounds (pcx_block_util.hpp)
+using namespace pcxblk;     // check, OnDevice, kDomain, the port-slab bounds, PortBlock (pcx_block_util.hpp)
 
 // the default port slab of every block of this port (comms_blocks.cpp's kPortSlabBytes; tests/test_preamble_cpu.py keeps them equal)
 constexpr size_t kPortSlabBytes = 64u << 20;
@@ -72,12 +72,11 @@ constexpr size_t kPortSlabBytes = 64u << 20;
  * |initializer setPortSlabBytes(portSlabBytes)
  * |initializer setDevice(device)
  **********************************************************************/
-class PreambleCorrelator : public Block {
+class PreambleCorrelator : public PortBlock {
 public:
-    PreambleCorrelator() : _preamble(1, 1), _threshold(1), _frameStartId("frameStart"), _device(-1), _slabBytes(kPortSlabBytes), _h(nullptr), _idx(4096)
+    PreambleCorrelator()
+        : PortBlock("PreambleCorrelator", kPortSlabBytes), _preamble(1, 1), _threshold(1), _frameStartId("frameStart"), _h(nullptr), _idx(4096)
     {
-        int cur = -1;
-        if (pcx_get_device(&cur) == PCX_OK) _device = cur;
         check(pcx_preamble_create(&_h), "PreambleCorrelator()");      // preamble {1}, threshold 1: PreambleCorrelator.cpp:72-73
         Block::setupInput(0, DType(typeid(unsigned char)), kDomain);
         Block::setupOutput(0, DType(typeid(unsigned char)), kDomain);
@@ -113,12 +112,8 @@ public:
     // EXTENSION (as every block of this port): the GPU that carries the block; the handle is created again there
     void setDevice(const size_t device)
     {
-        int n = 0;
-        check(pcx_device_count(&n), "PreambleCorrelator::setDevice()");
-        if (device >= (size_t)n)
-            throw InvalidArgumentException("PreambleCorrelator::setDevice(" + std::to_string(device) + ")",
-                                           "the process sees " + std::to_string(n) + " device(s)");
-        OnDevice on((int)device, "PreambleCorrelator::setDevice()");
+        const int d = checkedDevice(device);
+        OnDevice on(d, "PreambleCorrelator::setDevice()");
         pcx_preamble *fresh = nullptr;
         check(pcx_preamble_create(&fresh), "PreambleCorrelator::setDevice()");
         int rc = pcx_preamble_set_preamble(fresh, _preamble.data(), _preamble.size());
@@ -126,16 +121,11 @@ public:
         if (rc != PCX_OK) { pcx_preamble_destroy(fresh); check(rc, "PreambleCorrelator::setDevice()"); }
         pcx_preamble_destroy(_h);
         _h = fresh;
-        _device = (int)device;
+        _device = d;
     }
     size_t getDevice() const { return _device < 0 ? 0 : (size_t)_device; }
     // EXTENSION: the size of the port slabs the block's buffer managers hand out (an initializer)
-    void setPortSlabBytes(const size_t bytes)
-    {
-        if (bytes < kPortSlabMin || bytes > kPortSlabMax)
-            throw InvalidArgumentException("PreambleCorrelator::setPortSlabBytes(" + std::to_string(bytes) + ")", "64 KiB ... 1 GiB");
-        _slabBytes = bytes;
-    }
+    void setPortSlabBytes(const size_t bytes) { checkedSlab(bytes); }
     size_t getPortSlabBytes() const { return _slabBytes; }
 
     // work (PreambleCorrelator.cpp:114-154).  The reference takes the input buffer and posts it on the output; here k = min(in - P,
@@ -163,37 +153,11 @@ public:
         inPort->consume(positions);
         outPort->produce(positions);
     }
-#ifndef PCX_WITH_POTHOS
-    // (bundled runtime) page-locked slabs towards host blocks, device slabs between two blocks of this port
-    pcxfw::BufferManager::Sptr getInputBufferManager(const std::string &, const std::string &domain)
-    {
-        if (domain == kDomain) return pcxfw::BufferManager::Sptr();
-        return manager(false);
-    }
-    pcxfw::BufferManager::Sptr getOutputBufferManager(const std::string &, const std::string &domain)
-    {
-        OnDevice on(_device, "PreambleCorrelator::getOutputBufferManager()");
-        return manager(domain == kDomain);
-    }
-#endif
 
 private:
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr manager(bool device) const
-    {
-        pcxfw::BufferManagerArgs args;
-        args.bufferSize = _slabBytes;
-        args.numBuffers = 4;
-        if (device) args.device = true;
-        else args.pinned = true;
-        return pcxfw::BufferManager::make("generic", args);
-    }
-#endif
     std::vector<unsigned char> _preamble;
     unsigned _threshold;
     std::string _frameStartId;
-    int _device;
-    size_t _slabBytes;
     pcx_preamble *_h;
     std::vector<uint64_t> _idx;
 };

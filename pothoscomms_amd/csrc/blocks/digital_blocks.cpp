@@ -21,7 +21,7 @@ using pcxfw::RangeException;
 
 namespace {
 
-using namespace pcxblk;     // check, OnDevice, kDomain, the port-slab bounds (pcx_block_util.hpp)
+using namespace pcxblk;     // check, OnDevice, kDomain, the port-slab bounds, PortBlock (pcx_block_util.hpp)
 
 // the default port slab of every block of this port (comms_blocks.cpp's kPortSlabBytes; tests/test_scrambler_cpu.py keeps them equal)
 constexpr size_t kPortSlabBytes = 64u << 20;
@@ -111,14 +111,12 @@ constexpr size_t kPortSlabBytes = 64u << 20;
  * |initializer setDevice(device)
  **********************************************************************/
 // one class for both: they differ in what the multiplicative mode feeds back, which the handle knows
-class LfsrBlock : public Block {
+class LfsrBlock : public PortBlock {
 public:
     explicit LfsrBlock(bool descramble)
-        : _descramble(descramble), _who(descramble ? "Descrambler" : "Scrambler"), _poly(0x19), _seed(1), _mode("multiplicative"), _device(-1),
-          _slabBytes(kPortSlabBytes), _h(nullptr)
+        : PortBlock(descramble ? "Descrambler" : "Scrambler", kPortSlabBytes), _descramble(descramble), _poly(0x19), _seed(1),
+          _mode("multiplicative"), _h(nullptr)
     {
-        int cur = -1;
-        if (pcx_get_device(&cur) == PCX_OK) _device = cur;
         check(pcx_scrambler_create(descramble ? 1 : 0, &_h), _who + "()");      // multiplicative, seed 1, setPoly(0x19): Scrambler.cpp:58-61
         Block::setupInput(0, DType(typeid(unsigned char)), kDomain);
         Block::setupOutput(0, DType(typeid(unsigned char)), kDomain);
@@ -171,11 +169,8 @@ public:
     // polynomial, seed and mode, and the register starts over
     void setDevice(const size_t device)
     {
-        int n = 0;
-        check(pcx_device_count(&n), _who + "::setDevice()");
-        if (device >= (size_t)n)
-            throw InvalidArgumentException(_who + "::setDevice(" + std::to_string(device) + ")", "the process sees " + std::to_string(n) + " device(s)");
-        OnDevice on((int)device, "LfsrBlock::setDevice()");
+        const int d = checkedDevice(device);
+        OnDevice on(d, "LfsrBlock::setDevice()");
         pcx_scrambler *fresh = nullptr;
         check(pcx_scrambler_create(_descramble ? 1 : 0, &fresh), _who + "::setDevice()");
         int rc = pcx_scrambler_set_mode(fresh, modeCode(_mode));
@@ -184,16 +179,11 @@ public:
         if (rc != PCX_OK) { pcx_scrambler_destroy(fresh); check(rc, _who + "::setDevice()"); }
         pcx_scrambler_destroy(_h);
         _h = fresh;
-        _device = (int)device;
+        _device = d;
     }
     size_t getDevice() const { return _device < 0 ? 0 : (size_t)_device; }
     // EXTENSION: the size of the port slabs the block's buffer managers hand out (an initializer)
-    void setPortSlabBytes(const size_t bytes)
-    {
-        if (bytes < kPortSlabMin || bytes > kPortSlabMax)
-            throw InvalidArgumentException(_who + "::setPortSlabBytes(" + std::to_string(bytes) + ")", "64 KiB ... 1 GiB");
-        _slabBytes = bytes;
-    }
+    void setPortSlabBytes(const size_t bytes) { checkedSlab(bytes); }
     size_t getPortSlabBytes() const { return _slabBytes; }
 
     // work (Scrambler.cpp:154-181): min(in, out) elements, consumed and produced
@@ -207,19 +197,6 @@ public:
         inPort->consume(n);
         outPort->produce(n);
     }
-#ifndef PCX_WITH_POTHOS
-    // (bundled runtime) page-locked slabs towards host blocks, device slabs between two blocks of this port
-    pcxfw::BufferManager::Sptr getInputBufferManager(const std::string &, const std::string &domain)
-    {
-        if (domain == kDomain) return pcxfw::BufferManager::Sptr();
-        return manager(false);
-    }
-    pcxfw::BufferManager::Sptr getOutputBufferManager(const std::string &, const std::string &domain)
-    {
-        OnDevice on(_device, "LfsrBlock::getOutputBufferManager()");
-        return manager(domain == kDomain);
-    }
-#endif
 
 private:
     // the names the reference accepts; anything else is handed on as a code the ABI refuses (InvalidArgumentException)
@@ -229,23 +206,9 @@ private:
         if (mode == "multiplicative") return PCX_SCR_MULTIPLICATIVE;
         throw InvalidArgumentException(_who + "::set_mode()", "unknown mode: " + mode);
     }
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr manager(bool device) const
-    {
-        pcxfw::BufferManagerArgs args;
-        args.bufferSize = _slabBytes;
-        args.numBuffers = 4;
-        if (device) args.device = true;
-        else args.pinned = true;
-        return pcxfw::BufferManager::make("generic", args);
-    }
-#endif
     const bool _descramble;
-    const std::string _who;
     int64_t _poly, _seed;
     std::string _mode, _sync;
-    int _device;
-    size_t _slabBytes;
     pcx_scrambler *_h;
 };
 

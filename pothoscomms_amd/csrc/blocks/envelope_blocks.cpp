@@ -18,7 +18,7 @@ using pcxfw::InvalidArgumentException;
 
 namespace {
 
-using namespace pcxblk;     // parseElemType, check, OnDevice, kDomain, the port-slab bounds (pcx_block_util.hpp)
+using namespace pcxblk;     // parseElemType, check, OnDevice, kDomain, the port-slab bounds, PortBlock (pcx_block_util.hpp)
 
 // the default port slab of every block of this port (comms_blocks.cpp's kPortSlabBytes; tests/test_envelope_cpu.py keeps them equal)
 constexpr size_t kPortSlabBytes = 64u << 20;
@@ -75,13 +75,11 @@ constexpr size_t kPortSlabBytes = 64u << 20;
  * |initializer setPortSlabBytes(portSlabBytes)
  * |initializer setDevice(device)
  **********************************************************************/
-class EnvelopeDetector : public Block {
+class EnvelopeDetector : public PortBlock {
 public:
     EnvelopeDetector(const DType &dtype, int scalar, bool cplx)
-        : _scalar(scalar), _cplx(cplx), _attack(0), _release(0), _lookahead(0), _device(-1), _slabBytes(kPortSlabBytes), _h(nullptr)
+        : PortBlock("EnvelopeDetector", kPortSlabBytes), _scalar(scalar), _cplx(cplx), _attack(0), _release(0), _lookahead(0), _h(nullptr)
     {
-        int cur = -1;
-        if (pcx_get_device(&cur) == PCX_OK) _device = cur;
         check(pcx_envelope_create(scalar, cplx ? 1 : 0, &_h), "EnvelopeDetectorFactory(" + dtype.toString() + ")");
         Block::setupInput(0, dtype, kDomain);
         Block::setupOutput(0, DType("float32"), kDomain);
@@ -123,12 +121,8 @@ public:
     // the lookahead pushed again, and the envelope starts over from 0
     void setDevice(const size_t device)
     {
-        int n = 0;
-        check(pcx_device_count(&n), "EnvelopeDetector::setDevice()");
-        if (device >= (size_t)n)
-            throw InvalidArgumentException("EnvelopeDetector::setDevice(" + std::to_string(device) + ")",
-                                           "the process sees " + std::to_string(n) + " device(s)");
-        OnDevice on((int)device, "EnvelopeDetector::setDevice()");
+        const int d = checkedDevice(device);
+        OnDevice on(d, "EnvelopeDetector::setDevice()");
         pcx_envelope *fresh = nullptr;
         check(pcx_envelope_create(_scalar, _cplx ? 1 : 0, &fresh), "EnvelopeDetector::setDevice()");
         // a setter that was never called leaves its gains at 0, as the reference's constructor does
@@ -139,16 +133,11 @@ public:
         if (rc != PCX_OK) { pcx_envelope_destroy(fresh); check(rc, "EnvelopeDetector::setDevice()"); }
         pcx_envelope_destroy(_h);
         _h = fresh;
-        _device = (int)device;
+        _device = d;
     }
     size_t getDevice() const { return _device < 0 ? 0 : (size_t)_device; }
     // EXTENSION: the size of the port slabs the block's buffer managers hand out (an initializer)
-    void setPortSlabBytes(const size_t bytes)
-    {
-        if (bytes < kPortSlabMin || bytes > kPortSlabMax)
-            throw InvalidArgumentException("EnvelopeDetector::setPortSlabBytes(" + std::to_string(bytes) + ")", "64 KiB ... 1 GiB");
-        _slabBytes = bytes;
-    }
+    void setPortSlabBytes(const size_t bytes) { checkedSlab(bytes); }
     size_t getPortSlabBytes() const { return _slabBytes; }
 
     // no activate(): the envelope survives deactivate / activate, as in the reference
@@ -176,41 +165,21 @@ public:
 #ifndef PCX_WITH_POTHOS
         if (domain == kDomain) {
             OnDevice on(_device, "EnvelopeDetector::getInputBufferManager()");
-            return manager("circular", true);
+            return manager(true, "circular");
         }
-        return manager("circular", false);
+        return manager(false, "circular");
 #else
         (void)domain;
         return Pothos::BufferManager::make("circular");
 #endif
     }
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr getOutputBufferManager(const std::string &, const std::string &domain)
-    {
-        OnDevice on(_device, "EnvelopeDetector::getOutputBufferManager()");
-        return manager("generic", domain == kDomain);
-    }
-#endif
 
 private:
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr manager(const std::string &name, bool device) const
-    {
-        pcxfw::BufferManagerArgs args;
-        args.bufferSize = _slabBytes;
-        args.numBuffers = 4;
-        if (device) args.device = true;
-        else args.pinned = true;
-        return pcxfw::BufferManager::make(name, args);
-    }
-#endif
     const int _scalar;
     const bool _cplx;
     float _attack, _release;
     bool _attackSet = false, _releaseSet = false;
     size_t _lookahead;
-    int _device;
-    size_t _slabBytes;
     pcx_envelope *_h;
 };
 

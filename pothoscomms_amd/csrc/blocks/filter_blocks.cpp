@@ -18,7 +18,7 @@ using pcxfw::InvalidArgumentException;
 
 namespace {
 
-using namespace pcxblk;     // parseElemType, check, OnDevice, kDomain, the port-slab bounds (pcx_block_util.hpp)
+using namespace pcxblk;     // parseElemType, check, OnDevice, kDomain, the port-slab bounds, PortBlock (pcx_block_util.hpp)
 
 // the default port slab of every block of this port (comms_blocks.cpp's kPortSlabBytes; tests/test_dcremoval_cpu.py keeps them equal)
 constexpr size_t kPortSlabBytes = 64u << 20;
@@ -69,13 +69,11 @@ constexpr size_t kPortSlabBytes = 64u << 20;
  * |initializer setPortSlabBytes(portSlabBytes)
  * |initializer setDevice(device)
  **********************************************************************/
-class DCRemoval : public Block {
+class DCRemoval : public PortBlock {
 public:
     DCRemoval(const DType &dtype, int scalar, bool cplx)
-        : _scalar(scalar), _cplx(cplx), _averageSize(512), _cascadeSize(2), _device(-1), _slabBytes(kPortSlabBytes), _h(nullptr)
+        : PortBlock("DCRemoval", kPortSlabBytes), _scalar(scalar), _cplx(cplx), _averageSize(512), _cascadeSize(2), _h(nullptr)
     {
-        int cur = -1;
-        if (pcx_get_device(&cur) == PCX_OK) _device = cur;
         check(pcx_dcremoval_create(scalar, cplx ? 1 : 0, &_h), "DCRemovalFactory(" + dtype.toString() + ")");
         Block::setupInput(0, dtype, kDomain);
         Block::setupOutput(0, dtype, kDomain);
@@ -107,27 +105,19 @@ public:
     // carried state starts over, as after activate()
     void setDevice(const size_t device)
     {
-        int n = 0;
-        check(pcx_device_count(&n), "DCRemoval::setDevice()");
-        if (device >= (size_t)n)
-            throw InvalidArgumentException("DCRemoval::setDevice(" + std::to_string(device) + ")", "the process sees " + std::to_string(n) + " device(s)");
-        OnDevice on((int)device, "DCRemoval::setDevice()");
+        const int d = checkedDevice(device);
+        OnDevice on(d, "DCRemoval::setDevice()");
         pcx_dcremoval *fresh = nullptr;
         check(pcx_dcremoval_create(_scalar, _cplx ? 1 : 0, &fresh), "DCRemoval::setDevice()");
         const int rc = pcx_dcremoval_set_sizes(fresh, _averageSize, _cascadeSize);
         if (rc != PCX_OK) { pcx_dcremoval_destroy(fresh); check(rc, "DCRemoval::setDevice()"); }
         pcx_dcremoval_destroy(_h);
         _h = fresh;
-        _device = (int)device;
+        _device = d;
     }
     size_t getDevice() const { return _device < 0 ? 0 : (size_t)_device; }
     // EXTENSION: the size of the port slabs the block's buffer managers hand out (an initializer)
-    void setPortSlabBytes(const size_t bytes)
-    {
-        if (bytes < kPortSlabMin || bytes > kPortSlabMax)
-            throw InvalidArgumentException("DCRemoval::setPortSlabBytes(" + std::to_string(bytes) + ")", "64 KiB ... 1 GiB");
-        _slabBytes = bytes;
-    }
+    void setPortSlabBytes(const size_t bytes) { checkedSlab(bytes); }
     size_t getPortSlabBytes() const { return _slabBytes; }
 
     void activate() { check(pcx_dcremoval_reset(_h), "DCRemoval::activate()"); }
@@ -142,19 +132,6 @@ public:
         inPort->consume(N);
         outPort->produce(N);
     }
-#ifndef PCX_WITH_POTHOS
-    // (bundled runtime) page-locked slabs towards host blocks, device slabs between two blocks of this port
-    pcxfw::BufferManager::Sptr getInputBufferManager(const std::string &, const std::string &domain)
-    {
-        if (domain == kDomain) return pcxfw::BufferManager::Sptr();
-        return manager(false);
-    }
-    pcxfw::BufferManager::Sptr getOutputBufferManager(const std::string &, const std::string &domain)
-    {
-        OnDevice on(_device, "DCRemoval::getOutputBufferManager()");
-        return manager(domain == kDomain);
-    }
-#endif
 
 private:
     // new sizes, or (when the handle cannot allocate for them) the previous ones again, so that the block stays usable
@@ -171,22 +148,9 @@ private:
         if (rc == PCX_ERR_ARG) throw InvalidArgumentException(where, msg);
         throw pcxfw::Exception(where, msg);
     }
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr manager(bool device) const
-    {
-        pcxfw::BufferManagerArgs args;
-        args.bufferSize = _slabBytes;
-        args.numBuffers = 4;
-        if (device) args.device = true;
-        else args.pinned = true;
-        return pcxfw::BufferManager::make("generic", args);
-    }
-#endif
     const int _scalar;
     const bool _cplx;
     size_t _averageSize, _cascadeSize;
-    int _device;
-    size_t _slabBytes;
     pcx_dcremoval *_h;
 };
 

@@ -18,7 +18,7 @@ using pcxfw::InvalidArgumentException;
 
 namespace {
 
-using namespace pcxblk;     // parseElemType, check, OnDevice, kDomain, the port-slab bounds (pcx_block_util.hpp)
+using namespace pcxblk;     // parseElemType, check, OnDevice, kDomain, the port-slab bounds, PortBlock (pcx_block_util.hpp)
 
 // the default port slab of every block of this port (comms_blocks.cpp's kPortSlabBytes; tests/test_iir_cpu.py keeps them equal)
 constexpr size_t kPortSlabBytes = 64u << 20;
@@ -74,13 +74,11 @@ constexpr size_t kPortSlabBytes = 64u << 20;
  * |initializer setPortSlabBytes(portSlabBytes)
  * |initializer setDevice(device)
  **********************************************************************/
-class IIRFilter : public Block {
+class IIRFilter : public PortBlock {
 public:
     IIRFilter(const DType &dtype, int scalar, bool cplx)
-        : _scalar(scalar), _cplx(cplx), _waitTapsMode(false), _waitTapsArmed(false), _device(-1), _slabBytes(kPortSlabBytes), _h(nullptr)
+        : PortBlock("IIRFilter", kPortSlabBytes), _scalar(scalar), _cplx(cplx), _waitTapsMode(false), _waitTapsArmed(false), _h(nullptr)
     {
-        int cur = -1;
-        if (pcx_get_device(&cur) == PCX_OK) _device = cur;
         check(pcx_iir_create(scalar, cplx ? 1 : 0, &_h), "IIRFilterFactory(" + dtype.toString() + ")");
         _taps = {0.0676, 0.135, 0.0676, 1, -1.142, 0.412};       // the handle's own default (IIRFilter.cpp:57)
         Block::setupInput(0, dtype, kDomain);
@@ -112,27 +110,19 @@ public:
     // and the history starts over
     void setDevice(const size_t device)
     {
-        int n = 0;
-        check(pcx_device_count(&n), "IIRFilter::setDevice()");
-        if (device >= (size_t)n)
-            throw InvalidArgumentException("IIRFilter::setDevice(" + std::to_string(device) + ")", "the process sees " + std::to_string(n) + " device(s)");
-        OnDevice on((int)device, "IIRFilter::setDevice()");
+        const int d = checkedDevice(device);
+        OnDevice on(d, "IIRFilter::setDevice()");
         pcx_iir *fresh = nullptr;
         check(pcx_iir_create(_scalar, _cplx ? 1 : 0, &fresh), "IIRFilter::setDevice()");
         const int rc = pcx_iir_set_taps(fresh, _taps.data(), _taps.size());
         if (rc != PCX_OK) { pcx_iir_destroy(fresh); check(rc, "IIRFilter::setDevice()"); }
         pcx_iir_destroy(_h);
         _h = fresh;
-        _device = (int)device;
+        _device = d;
     }
     size_t getDevice() const { return _device < 0 ? 0 : (size_t)_device; }
     // EXTENSION: the size of the port slabs the block's buffer managers hand out (an initializer)
-    void setPortSlabBytes(const size_t bytes)
-    {
-        if (bytes < kPortSlabMin || bytes > kPortSlabMax)
-            throw InvalidArgumentException("IIRFilter::setPortSlabBytes(" + std::to_string(bytes) + ")", "64 KiB ... 1 GiB");
-        _slabBytes = bytes;
-    }
+    void setPortSlabBytes(const size_t bytes) { checkedSlab(bytes); }
     size_t getPortSlabBytes() const { return _slabBytes; }
 
     // activate (IIRFilter.cpp:77-80): the history back to zero, waitTaps armed
@@ -154,38 +144,12 @@ public:
         inPort->consume(N);
         outPort->produce(N);
     }
-#ifndef PCX_WITH_POTHOS
-    // (bundled runtime) page-locked slabs towards host blocks, device slabs between two blocks of this port
-    pcxfw::BufferManager::Sptr getInputBufferManager(const std::string &, const std::string &domain)
-    {
-        if (domain == kDomain) return pcxfw::BufferManager::Sptr();
-        return manager(false);
-    }
-    pcxfw::BufferManager::Sptr getOutputBufferManager(const std::string &, const std::string &domain)
-    {
-        OnDevice on(_device, "IIRFilter::getOutputBufferManager()");
-        return manager(domain == kDomain);
-    }
-#endif
 
 private:
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr manager(bool device) const
-    {
-        pcxfw::BufferManagerArgs args;
-        args.bufferSize = _slabBytes;
-        args.numBuffers = 4;
-        if (device) args.device = true;
-        else args.pinned = true;
-        return pcxfw::BufferManager::make("generic", args);
-    }
-#endif
     const int _scalar;
     const bool _cplx;
     std::vector<double> _taps;
     bool _waitTapsMode, _waitTapsArmed;
-    int _device;
-    size_t _slabBytes;
     pcx_iir *_h;
 };
 

@@ -26,7 +26,7 @@ using pcxfw::InvalidArgumentException;
 
 namespace {
 
-using namespace pcxblk;     // check, OnDevice, kDomain, the port-slab bounds (pcx_block_util.hpp)
+using namespace pcxblk;     // check, OnDevice, kDomain, the port-slab bounds, PortBlock (pcx_block_util.hpp)
 
 // the default port slab of every block of this port (comms_blocks.cpp's kPortSlabBytes; tests/test_repack_cpu.py keeps them equal)
 constexpr size_t kPortSlabBytes = 64u << 20;
@@ -192,12 +192,10 @@ const char *const kNames[4] = {"BitsToSymbols", "SymbolsToBits", "BytesToSymbols
  * |initializer setDevice(device)
  **********************************************************************/
 // one class for the four: the handle knows which conversion it runs and which group the reference reserves for it
-class RepackBlock : public Block {
+class RepackBlock : public PortBlock {
 public:
-    explicit RepackBlock(int kind) : _kind(kind), _who(kNames[kind]), _h(nullptr), _device(-1), _slabBytes(kPortSlabBytes)
+    explicit RepackBlock(int kind) : PortBlock(kNames[kind], kPortSlabBytes), _kind(kind), _h(nullptr)
     {
-        int cur = -1;
-        if (pcx_get_device(&cur) == PCX_OK) _device = cur;
         check(pcx_repack_create(kind, &_h), _who + "()");      // modulus 1; MSBit for the bit kinds, LSBit for the byte kinds
         Block::setupInput(0, DType(typeid(unsigned char)), kDomain);
         Block::setupOutput(0, DType(typeid(unsigned char)), kDomain);
@@ -212,19 +210,6 @@ public:
     }
     ~RepackBlock() { pcx_repack_destroy(_h); }
 
-#ifndef PCX_WITH_POTHOS
-    // (bundled runtime) page-locked slabs towards host blocks, device slabs between two blocks of this port
-    pcxfw::BufferManager::Sptr getInputBufferManager(const std::string &, const std::string &domain)
-    {
-        if (domain == kDomain) return pcxfw::BufferManager::Sptr();
-        return manager(false);
-    }
-    pcxfw::BufferManager::Sptr getOutputBufferManager(const std::string &, const std::string &domain)
-    {
-        OnDevice on(_device, "RepackBlock::getOutputBufferManager()");
-        return manager(domain == kDomain);
-    }
-#endif
 
     // setModulus (:64-71 of BitsToSymbols.cpp, the same check in the other three): the handle refuses anything outside 1 ... 8 and
     // keeps the previous value.  The reference's parameter is an unsigned char; a size_t that would narrow into 1 ... 8 is refused here.
@@ -254,11 +239,8 @@ public:
     // EXTENSION (as every block of this port): the GPU that carries the block; the handle is created again there with its settings
     void setDevice(const size_t device)
     {
-        int n = 0;
-        check(pcx_device_count(&n), _who + "::setDevice()");
-        if (device >= (size_t)n)
-            throw InvalidArgumentException(_who + "::setDevice(" + std::to_string(device) + ")", "the process sees " + std::to_string(n) + " device(s)");
-        OnDevice on((int)device, "RepackBlock::setDevice()");
+        const int d = checkedDevice(device);
+        OnDevice on(d, "RepackBlock::setDevice()");
         unsigned mod = 1;
         int msb = 0;
         check(pcx_repack_get_modulus(_h, &mod), _who + "::setDevice()");
@@ -269,16 +251,11 @@ public:
         pcx_repack_set_bit_order(fresh, msb);
         pcx_repack_destroy(_h);
         _h = fresh;
-        _device = (int)device;
+        _device = d;
     }
     size_t getDevice() const { return _device < 0 ? 0 : (size_t)_device; }
     // EXTENSION: the size of the port slabs the block's buffer managers hand out (an initializer)
-    void setPortSlabBytes(const size_t bytes)
-    {
-        if (bytes < kPortSlabMin || bytes > kPortSlabMax)
-            throw InvalidArgumentException(_who + "::setPortSlabBytes(" + std::to_string(bytes) + ")", "64 KiB ... 1 GiB");
-        _slabBytes = bytes;
-    }
+    void setPortSlabBytes(const size_t bytes) { checkedSlab(bytes); }
     size_t getPortSlabBytes() const { return _slabBytes; }
 
     // work (BitsToSymbols.cpp:114-146, SymbolsToBits.cpp:112-143, BytesToSymbols.cpp:121-156, SymbolsToBytes.cpp:124-159): the
@@ -310,22 +287,8 @@ public:
     }
 
 private:
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr manager(bool device) const
-    {
-        pcxfw::BufferManagerArgs args;
-        args.bufferSize = _slabBytes;
-        args.numBuffers = 4;
-        if (device) args.device = true;
-        else args.pinned = true;
-        return pcxfw::BufferManager::make("generic", args);
-    }
-#endif
     const int _kind;
-    const std::string _who;
     pcx_repack *_h;
-    int _device;
-    size_t _slabBytes;
 };
 
 Block *BitsToSymbolsFactory() { return new RepackBlock(PCX_REPACK_BITS_TO_SYMBOLS); }

@@ -27,7 +27,7 @@ using pcxfw::InvalidArgumentException;
 
 namespace {
 
-using namespace pcxblk;     // check, OnDevice, kDomain, parseElemType, the port-slab bounds (pcx_block_util.hpp)
+using namespace pcxblk;     // check, OnDevice, kDomain, parseElemType, the port-slab bounds, PortBlock (pcx_block_util.hpp)
 
 // the default port slab of every block of this port (comms_blocks.cpp's kPortSlabBytes; tests/test_symbols_cpu.py keeps them equal)
 constexpr size_t kPortSlabBytes = 64u << 20;
@@ -75,60 +75,6 @@ double getScalar(int scalar, const unsigned char *src)
     }
     return getScalar<int8_t>(src);
 }
-
-// what the four blocks share as every block of this port does: the device, the port slabs and their managers
-class SymbolBase : public Block {
-public:
-    explicit SymbolBase(const std::string &who) : _who(who), _device(-1), _slabBytes(kPortSlabBytes)
-    {
-        int cur = -1;
-        if (pcx_get_device(&cur) == PCX_OK) _device = cur;
-    }
-#ifndef PCX_WITH_POTHOS
-    // (bundled runtime) page-locked slabs towards host blocks, device slabs between two blocks of this port
-    pcxfw::BufferManager::Sptr getInputBufferManager(const std::string &, const std::string &domain)
-    {
-        if (domain == kDomain) return pcxfw::BufferManager::Sptr();
-        return manager(false);
-    }
-    pcxfw::BufferManager::Sptr getOutputBufferManager(const std::string &, const std::string &domain)
-    {
-        OnDevice on(_device, "SymbolBase::getOutputBufferManager()");
-        return manager(domain == kDomain);
-    }
-#endif
-
-protected:
-    // the device a setDevice() asks for, checked against what the process sees
-    int checkedDevice(const size_t device) const
-    {
-        int n = 0;
-        check(pcx_device_count(&n), _who + "::setDevice()");
-        if (device >= (size_t)n)
-            throw InvalidArgumentException(_who + "::setDevice(" + std::to_string(device) + ")", "the process sees " + std::to_string(n) + " device(s)");
-        return (int)device;
-    }
-    void checkedSlab(const size_t bytes)
-    {
-        if (bytes < kPortSlabMin || bytes > kPortSlabMax)
-            throw InvalidArgumentException(_who + "::setPortSlabBytes(" + std::to_string(bytes) + ")", "64 KiB ... 1 GiB");
-        _slabBytes = bytes;
-    }
-#ifndef PCX_WITH_POTHOS
-    pcxfw::BufferManager::Sptr manager(bool device) const
-    {
-        pcxfw::BufferManagerArgs args;
-        args.bufferSize = _slabBytes;
-        args.numBuffers = 4;
-        if (device) args.device = true;
-        else args.pinned = true;
-        return pcxfw::BufferManager::make("generic", args);
-    }
-#endif
-    const std::string _who;
-    int _device;
-    size_t _slabBytes;
-};
 
 /***********************************************************************
  * |PothosDoc Symbol Mapper
@@ -217,10 +163,10 @@ protected:
  * |initializer setDevice(device)
  **********************************************************************/
 // one class for both: the mapper writes the stream type, the slicer reads it; maps cross as complex doubles and are narrowed here
-class MapBlock : public SymbolBase {
+class MapBlock : public PortBlock {
 public:
     MapBlock(const DType &dtype, int scalar, bool cplx, bool slicer)
-        : SymbolBase(slicer ? "SymbolSlicer" : "SymbolMapper"), _slicer(slicer), _scalar(scalar), _cplx(cplx), _m(nullptr), _s(nullptr)
+        : PortBlock(slicer ? "SymbolSlicer" : "SymbolMapper", kPortSlabBytes), _slicer(slicer), _scalar(scalar), _cplx(cplx), _m(nullptr), _s(nullptr)
     {
         create(_m, _s, _who + "Factory(" + dtype.toString() + ")");        // the map is {1}: SymbolMapper.cpp:58, SymbolSlicer.cpp:64
         Block::setupInput(0, slicer ? dtype : DType(typeid(unsigned char)), kDomain);
@@ -386,9 +332,10 @@ private:
  * |initializer setDevice(device)
  **********************************************************************/
 // one class for both: the handle knows which recurrence it runs
-class DiffBlock : public SymbolBase {
+class DiffBlock : public PortBlock {
 public:
-    explicit DiffBlock(bool decode) : SymbolBase(decode ? "DifferentialDecoder" : "DifferentialEncoder"), _decode(decode), _symbols(2), _h(nullptr)
+    explicit DiffBlock(bool decode)
+        : PortBlock(decode ? "DifferentialDecoder" : "DifferentialEncoder", kPortSlabBytes), _decode(decode), _symbols(2), _h(nullptr)
     {
         check(pcx_diffcode_create(decode ? 1 : 0, &_h), _who + "()");      // symbols 2, the carried byte 0: :30 of either file
         Block::setupInput(0, DType(typeid(unsigned char)), kDomain);

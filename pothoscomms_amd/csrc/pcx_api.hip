@@ -1,6 +1,8 @@
 // pcx_api.hip -- the extern "C" boundary of libpcx_hip.so (include/pcx.h), part 1: errors, devices, memory, page-locking, the
-// link probe, and what every handle shares (pcx_host.hpp): control-plane uploads, execution contexts, staging of pageable
-// host buffers.  The handles themselves: pcx_fir_api.hip (FIR, fused chain), pcx_fft_api.hip (FFT, FreqDemod, the maps).
+// link probe, and what every handle shares (pcx_host.hpp): control-plane uploads, execution contexts with the stream of a reset and
+// the read-back of carried state, the overlap rule of in and out, staging of pageable host buffers (host_call, the one form of a
+// staged call, is a template there).  The handles themselves: pcx_fir_api.hip (FIR, fused chain), pcx_fft_api.hip (FFT, FreqDemod,
+// the maps) and one pcx_*_api.hip per further block.
 // Host-side only: all arithmetic on stream data happens in the HIP kernels.
 #include <algorithm>
 #include <chrono>
@@ -474,6 +476,32 @@ int ctx_quiesce(ExecCtx &c)
 {
     if (c.have_last) PCX_HIP(hipStreamSynchronize(c.last));
     return PCX_OK;
+}
+// (behind the handle's previous call and ahead of its next, whichever stream that arrives on)
+int ctx_state_stream(ExecCtx &c, hipStream_t *out)
+{
+    if (c.have_last) *out = c.last;
+    else PCX_TRY(ctx_own_stream(c, out));
+    return ctx_enter(c, *out);
+}
+int ctx_read_back(ExecCtx &c, void *dst, const void *src, size_t bytes)
+{
+    PCX_TRY(ctx_quiesce(c));
+    PCX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return PCX_OK;
+}
+bool device_reachable()
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return n > 0;
+}
+size_t elem_bytes(int scalar, bool cplx) { return (size_t)scalar_bytes(scalar) * (cplx ? 2 : 1); }
+bool buffers_ok(const void *in, size_t in_bytes, const void *out, size_t out_bytes, bool in_place)
+{
+    const char *a = static_cast<const char *>(in), *b = static_cast<const char *>(out);
+    if (in_place && a == b) return true;
+    return a + in_bytes <= b || b + out_bytes <= a;
 }
 
 // Device-visible alias of a HOST pointer when it is page-locked (pcx_host_alloc / hipHostMalloc / hipHostRegister; any

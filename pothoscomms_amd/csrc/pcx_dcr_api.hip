@@ -118,7 +118,7 @@ int pcx_dcremoval_create(int scalar, int is_complex, pcx_dcremoval **out)
     if (!h) { set_error("out of memory"); return PCX_ERR_STATE; }
     h->p.scalar = scalar;
     h->p.cplx = is_complex != 0;
-    h->elem = (size_t)scalar_bytes(scalar) * (is_complex ? 2 : 1);
+    h->elem = elem_bytes(scalar, h->p.cplx);
     DeviceScope dev_scope(h->cx.device);
     const int rc = dcr_configure(h, 512, 2);        // DCRemoval.cpp's initial state
     if (rc != PCX_OK) { delete h; return rc; }
@@ -144,9 +144,8 @@ int pcx_dcremoval_reset(pcx_dcremoval *h)
     PCX_CHECK_ARG(h, "null handle");
     DeviceScope dev_scope(h->cx.device);
     if (!h->ready) { set_error("DCRemoval::activate(): the handle has no sizes (the last set_sizes failed)"); return PCX_ERR_STATE; }
-    hipStream_t st = h->cx.have_last ? h->cx.last : nullptr;
-    if (!h->cx.have_last) PCX_TRY(ctx_own_stream(h->cx, &st));
-    PCX_TRY(ctx_enter(h->cx, st));
+    hipStream_t st;
+    PCX_TRY(ctx_state_stream(h->cx, &st));
     return dcr_zero_state(h, st);
 }
 int pcx_dcremoval_process_dev(pcx_dcremoval *h, const void *in_dev, void *out_dev, size_t n, void *stream)
@@ -195,12 +194,5 @@ int pcx_dcremoval_process(pcx_dcremoval *h, const void *in, void *out, size_t n)
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t bytes = n * h->elem;
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, bytes, h->wsOut));
-    PCX_TRY(stage_in(in, bytes, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, bytes, h->wsOut, &dout, &staged));
-    PCX_TRY(pcx_dcremoval_process_dev(h, din, dout, n, st));
-    return stage_out_end(out, bytes, h->wsOut, staged, st);
+    return host_call(h, in, bytes, out, bytes, [&](const void *din, void *dout, hipStream_t st) { return pcx_dcremoval_process_dev(h, din, dout, n, st); });
 }

@@ -54,7 +54,7 @@ int pcx_envelope_create(int scalar, int is_complex, pcx_envelope **out)
     if (!h) { set_error("out of memory"); return PCX_ERR_STATE; }
     h->p.scalar = scalar;
     h->p.cplx = is_complex != 0;
-    h->elem = (size_t)scalar_bytes(scalar) * (is_complex ? 2 : 1);
+    h->elem = elem_bytes(scalar, h->p.cplx);
     env_shape(h);                                   // EnvelopeDetector.cpp:56-73: every gain 0, envelope 0, lookahead 0
     DeviceScope dev_scope(h->cx.device);
     const size_t chunks = kSlice / (size_t)kChunkMin;
@@ -122,30 +122,22 @@ int pcx_envelope_reset(pcx_envelope *h)
 {
     PCX_CHECK_ARG(h, "null handle");
     DeviceScope dev_scope(h->cx.device);
-    hipStream_t st = h->cx.have_last ? h->cx.last : nullptr;
-    if (!h->cx.have_last) PCX_TRY(ctx_own_stream(h->cx, &st));
-    PCX_TRY(ctx_enter(h->cx, st));
+    hipStream_t st;
+    PCX_TRY(ctx_state_stream(h->cx, &st));
     return launch_zero_words(h->state.p, h->state.cap / 4, st);
-}
-
-// what the handle's last call left on the device, once that call is complete
-static int env_read(pcx_envelope *h, void *dst, const DevBuf &src, size_t bytes)
-{
-    DeviceScope dev_scope(h->cx.device);
-    if (h->cx.have_last) PCX_HIP(hipStreamSynchronize(h->cx.last));
-    PCX_HIP(hipMemcpy(dst, src.p, bytes, hipMemcpyDeviceToHost));
-    return PCX_OK;
 }
 int pcx_envelope_get_state(pcx_envelope *h, float *envelope)
 {
     PCX_CHECK_ARG(h && envelope, "null argument");
-    return env_read(h, envelope, h->state, sizeof(float));
+    DeviceScope dev_scope(h->cx.device);
+    return ctx_read_back(h->cx, envelope, h->state.p, sizeof(float));
 }
 int pcx_envelope_get_stats(pcx_envelope *h, uint64_t *chunks, uint64_t *repaired, uint64_t *resolved)
 {
     PCX_CHECK_ARG(h && chunks && repaired && resolved, "null argument");
     unsigned long long c[4];
-    PCX_TRY(env_read(h, c, h->cnt, sizeof(c)));
+    DeviceScope dev_scope(h->cx.device);
+    PCX_TRY(ctx_read_back(h->cx, c, h->cnt.p, sizeof(c)));
     *chunks = c[1];
     *repaired = c[2];
     *resolved = c[3];
@@ -180,12 +172,6 @@ int pcx_envelope_process(pcx_envelope *h, const void *in, void *out, size_t n)
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t in_bytes = (n + h->lookahead) * h->elem, out_bytes = n * sizeof(float);
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, out_bytes, h->wsOut));
-    PCX_TRY(stage_in(in, in_bytes, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, out_bytes, h->wsOut, &dout, &staged));
-    PCX_TRY(pcx_envelope_process_dev(h, din, dout, n, st));
-    return stage_out_end(out, out_bytes, h->wsOut, staged, st);
+    return host_call(h, in, in_bytes, out, out_bytes,
+                     [&](const void *din, void *dout, hipStream_t st) { return pcx_envelope_process_dev(h, din, dout, n, st); });
 }

@@ -378,14 +378,7 @@ int pcx_fft_transform(pcx_fft *h, const void *in, void *out, size_t nframes)
     if (nframes == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t bytes = nframes * h->nbins * 2 * (size_t)scalar_bytes(h->scalar);
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, bytes, h->wsOut));
-    PCX_TRY(stage_in(in, bytes, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, bytes, h->wsOut, &dout, &staged));
-    PCX_TRY(pcx_fft_transform_dev(h, din, dout, nframes, st));
-    return stage_out_end(out, bytes, h->wsOut, staged, st);
+    return host_call(h, in, bytes, out, bytes, [&](const void *din, void *dout, hipStream_t st) { return pcx_fft_transform_dev(h, din, dout, nframes, st); });
 }
 
 /* ===================================================================== *
@@ -417,10 +410,9 @@ int pcx_freqdemod_reset(pcx_freqdemod *h)
     PCX_CHECK_ARG(h, "null handle");
     DeviceScope dev_scope(h->cx.device);
     // _prev = 0, FreqDemod.cpp:46 -- enqueued behind the handle's previous call (its kernel still reads/writes prev) and
-    // ahead of the next one, whatever stream that arrives on (ctx_enter)
-    hipStream_t st = h->cx.have_last ? h->cx.last : nullptr;
-    if (!h->cx.have_last) PCX_TRY(ctx_own_stream(h->cx, &st));
-    PCX_TRY(ctx_enter(h->cx, st));
+    // ahead of the next one, whatever stream that arrives on (ctx_state_stream)
+    hipStream_t st;
+    PCX_TRY(ctx_state_stream(h->cx, &st));
     PCX_TRY(launch_zero_words(h->prev.p, 16, st));   // (a kernel, not hipMemsetAsync: see launch_zero_words)
     h->cur = 0;
     return PCX_OK;
@@ -459,17 +451,10 @@ int pcx_freqdemod_process(pcx_freqdemod *h, const void *in, void *out, size_t n)
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t sb = (size_t)scalar_bytes(h->scalar);
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, n * sb, h->wsOut));
-    PCX_TRY(stage_in(in, n * 2 * sb, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, n * sb, h->wsOut, &dout, &staged));
-    {
+    return host_call(h, in, n * 2 * sb, out, n * sb, [&](const void *din, void *dout, hipStream_t st) {
         LinkBound shape(in, out, nullptr, 64);
-        PCX_TRY(pcx_freqdemod_process_dev(h, din, dout, n, st));
-    }
-    return stage_out_end(out, n * sb, h->wsOut, staged, st);
+        return pcx_freqdemod_process_dev(h, din, dout, n, st);
+    });
 }
 
 /* ===================================================================== *

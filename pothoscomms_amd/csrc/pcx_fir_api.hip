@@ -819,9 +819,8 @@ int pcx_fmchain_reset(pcx_fmchain *h)
     PCX_CHECK_ARG(h, "null handle");
     DeviceScope dev_scope(h->cx.device);
     // as pcx_freqdemod_reset: ordered behind the previous call and ahead of the next one
-    hipStream_t st = h->cx.have_last ? h->cx.last : nullptr;
-    if (!h->cx.have_last) PCX_TRY(ctx_own_stream(h->cx, &st));
-    PCX_TRY(ctx_enter(h->cx, st));
+    hipStream_t st;
+    PCX_TRY(ctx_state_stream(h->cx, &st));
     PCX_TRY(launch_zero_words(h->prev.p, 16, st));   // (a kernel, not hipMemsetAsync: see launch_zero_words)
     h->cur = 0;
     return PCX_OK;
@@ -967,20 +966,12 @@ int pcx_fmchain_process(pcx_fmchain *h, const void *in, size_t in_elems, void *o
     if (N == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t used = N + h->K - 1;
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, N * 4, h->wsOut));
-    PCX_TRY(stage_in(in, used * 8, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, N * 4, h->wsOut, &dout, &staged));
-    const unsigned keep_slots = h->slots;
-    int rc;
-    {
+    return host_call(h, in, used * 8, out, N * 4, [&](const void *din, void *dout, hipStream_t st) {
         LinkBound shape(in, out);                      // (pcx_fir_process: a link-bound call's launch shape)
+        const unsigned keep_slots = h->slots;
         if (g_link_grid) h->slots = g_link_grid;
-        rc = pcx_fmchain_process_dev(h, din, used, dout, N, consumed, produced, st);
-    }
-    h->slots = keep_slots;
-    PCX_TRY(rc);
-    return stage_out_end(out, N * 4, h->wsOut, staged, st);
+        const int rc = pcx_fmchain_process_dev(h, din, used, dout, N, consumed, produced, st);
+        h->slots = keep_slots;
+        return rc;
+    });
 }

@@ -1,6 +1,8 @@
-// pcx_host.hpp -- what the translation units behind include/pcx.h share (pcx_api.hip implements it; pcx_fir_api.hip and
-// pcx_fft_api.hip hold the handles): argument checks, control-plane uploads, a handle's execution context, the staging of pageable
-// host buffers and the launch shape of calls on page-locked ones.  Not installed.
+// pcx_host.hpp -- what the translation units behind include/pcx.h share (pcx_api.hip implements it; the pcx_*_api.hip files hold
+// the handles): argument checks, control-plane uploads, a handle's execution context and the calls on it that every handle makes
+// the same way (the stream of a reset, the read-back of carried state, the overlap rule of in and out), the staging of pageable
+// host buffers with host_call, the one form of a staged host-pointer call, and the launch shape of calls on page-locked buffers.
+// Not installed.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -75,6 +77,16 @@ struct ExecCtx {
 int ctx_own_stream(ExecCtx &c, hipStream_t *out);
 int ctx_enter(ExecCtx &c, hipStream_t st);
 int ctx_quiesce(ExecCtx &c);
+// the stream a state-changing control call (a reset) enqueues on: the handle's last stream, else its own; entered on return
+int ctx_state_stream(ExecCtx &c, hipStream_t *out);
+// what the handle's last call left at `src` on the device, once that call is complete
+int ctx_read_back(ExecCtx &c, void *dst, const void *src, size_t bytes);
+// is there a device to build tables on now (else they are built at the first computing call)
+bool device_reachable();
+// bytes of one stream element
+size_t elem_bytes(int scalar, bool cplx);
+// may a call read `in` and write `out`: no byte shared, or (in_place) the very same buffer
+bool buffers_ok(const void *in, size_t in_bytes, const void *out, size_t out_bytes, bool in_place);
 size_t stage_piece(size_t bytes);
 void stage_copy(void *dst, const void *src, size_t bytes);
 int stage_reserve(const void *host, size_t bytes, StageBuf &ws);
@@ -83,6 +95,21 @@ int stage_out_begin(void *host, size_t bytes, StageBuf &ws, void **dev, bool *st
 int stage_out_first(StageBuf &ws, size_t bytes, bool staged, hipStream_t st);
 int stage_out_rest(void *host, StageBuf &ws, size_t bytes, bool staged, hipStream_t st);
 int stage_out_end(void *host, size_t bytes, StageBuf &ws, bool staged, hipStream_t st);
+// A call of one handle (cx, wsIn, wsOut) from host pointers, on the handle's own stream: staged through the handle's workspaces, or
+// in place on page-locked memory.  dev_call(din, dout, st) enqueues the work and returns a status; the result is in `out` on return.
+// (call with the handle's DeviceScope alive)
+template <typename H, typename F>
+int host_call(H *h, const void *in, size_t in_bytes, void *out, size_t out_bytes, F &&dev_call)
+{
+    hipStream_t st;
+    PCX_TRY(ctx_own_stream(h->cx, &st));
+    const void *din; void *dout; bool staged;
+    PCX_TRY(stage_reserve(out, out_bytes, h->wsOut));
+    PCX_TRY(stage_in(in, in_bytes, h->wsIn, st, &din));
+    PCX_TRY(stage_out_begin(out, out_bytes, h->wsOut, &dout, &staged));
+    PCX_TRY(dev_call(din, dout, st));
+    return stage_out_end(out, out_bytes, h->wsOut, staged, st);
+}
 bool host_page_locked(const void *p);
 int drain_chunks(size_t bytes);
 int drain_setup(ExecCtx &c, int nchunks);

@@ -82,13 +82,6 @@ struct pcx_iir {
     StageBuf wsIn, wsOut;
 };
 
-// the apply and finish kernels read a slice's inputs after outputs have been written: no byte of the two buffers may be shared
-static bool iir_disjoint(const void *in, const void *out, size_t bytes)
-{
-    const char *a = static_cast<const char *>(in), *b = static_cast<const char *>(out);
-    return a + bytes <= b || b + bytes <= a;
-}
-
 static int iir_zero_state(pcx_iir *h, hipStream_t st)
 {
     PCX_TRY(launch_zero_words(h->xh.p, h->xh.cap / 4, st));
@@ -215,7 +208,7 @@ int pcx_iir_create(int scalar, int is_complex, pcx_iir **out)
     if (!h) { set_error("out of memory"); return PCX_ERR_STATE; }
     h->p.scalar = scalar;
     h->p.cplx = is_complex != 0;
-    h->elem = (size_t)scalar_bytes(scalar) * (is_complex ? 2 : 1);
+    h->elem = elem_bytes(scalar, h->p.cplx);
     DeviceScope dev_scope(h->cx.device);
     const size_t tiles = iir_slice() / iir_tile(), hist = (size_t)iir_history();
     int rc = h->tab.ensure(tab_doubles(kMaxNB) * sizeof(double));
@@ -258,9 +251,8 @@ int pcx_iir_reset(pcx_iir *h)
 {
     PCX_CHECK_ARG(h, "null handle");
     DeviceScope dev_scope(h->cx.device);
-    hipStream_t st = h->cx.have_last ? h->cx.last : nullptr;
-    if (!h->cx.have_last) PCX_TRY(ctx_own_stream(h->cx, &st));
-    PCX_TRY(ctx_enter(h->cx, st));
+    hipStream_t st;
+    PCX_TRY(ctx_state_stream(h->cx, &st));
     return iir_zero_state(h, st);
 }
 
@@ -270,7 +262,8 @@ int pcx_iir_process_dev(pcx_iir *h, const void *in_dev, void *out_dev, size_t n,
     PCX_CHECK_ARG(h, "null handle");
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
-    PCX_CHECK_ARG(iir_disjoint(in_dev, out_dev, n * h->elem), "iir_filter: out overlaps in (out == in included)");
+    // the apply and finish kernels read a slice's inputs after outputs have been written: no byte of the two buffers may be shared
+    PCX_CHECK_ARG(buffers_ok(in_dev, n * h->elem, out_dev, n * h->elem, false), "iir_filter: out overlaps in (out == in included)");
     DeviceScope dev_scope(h->cx.device);
     hipStream_t st = as_stream(stream);
     PCX_TRY(ctx_enter(h->cx, st));
@@ -292,14 +285,7 @@ int pcx_iir_process(pcx_iir *h, const void *in, void *out, size_t n)
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t bytes = n * h->elem;
-    PCX_CHECK_ARG(iir_disjoint(in, out, bytes), "iir_filter: out overlaps in (out == in included)");
+    PCX_CHECK_ARG(buffers_ok(in, bytes, out, bytes, false), "iir_filter: out overlaps in (out == in included)");
     DeviceScope dev_scope(h->cx.device);
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, bytes, h->wsOut));
-    PCX_TRY(stage_in(in, bytes, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, bytes, h->wsOut, &dout, &staged));
-    PCX_TRY(pcx_iir_process_dev(h, din, dout, n, st));
-    return stage_out_end(out, bytes, h->wsOut, staged, st);
+    return host_call(h, in, bytes, out, bytes, [&](const void *din, void *dout, hipStream_t st) { return pcx_iir_process_dev(h, din, dout, n, st); });
 }

@@ -21,12 +21,6 @@ struct pcx_preamble {
 };
 
 namespace {
-bool device_reachable()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return n > 0;
-}
 void configure(pcx_preamble *h)
 {
     h->p.P = h->pre.size();
@@ -133,9 +127,9 @@ int pcx_preamble_process_dev(pcx_preamble *h, const void *in_dev, size_t n_in, v
     const size_t npos = n_in > P ? n_in - P : 0;
     PCX_CHECK_ARG(!npos || in_dev, "null buffer");
     PCX_CHECK_ARG(!idx_cap || idx_dev, "null index buffer");
+    PCX_CHECK_ARG(!npos || !out_dev || buffers_ok(in_dev, n_in, out_dev, npos, true), "preamble correlator: out overlaps in (in place means out == in)");
     const char *in = static_cast<const char *>(in_dev);
     char *out = static_cast<char *>(out_dev);
-    PCX_CHECK_ARG(!npos || !out || in == out || in + n_in <= out || out + npos <= in, "preamble correlator: out overlaps in (in place means out == in)");
     DeviceScope dev_scope(h->cx.device);
     PCX_TRY(prepare(h));
     hipStream_t st = as_stream(stream);
@@ -227,15 +221,10 @@ int pcx_preamble_distances(pcx_preamble *h, const void *in, size_t n_in, uint32_
     const size_t npos = n_in - P, bytes = npos * sizeof(uint32_t);
     PCX_CHECK_ARG(in && dist, "null buffer");
     DeviceScope dev_scope(h->cx.device);
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
     PCX_TRY(prepare(h));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(dist, bytes, h->wsOut));
-    PCX_TRY(stage_in(in, n_in, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(dist, bytes, h->wsOut, &dout, &staged));
-    PCX_TRY(pcx_preamble_distances_dev(h, din, n_in, static_cast<uint32_t *>(dout), st));
-    PCX_TRY(stage_out_end(dist, bytes, h->wsOut, staged, st));
+    PCX_TRY(host_call(h, in, n_in, dist, bytes, [&](const void *din, void *dout, hipStream_t st) {
+        return pcx_preamble_distances_dev(h, din, n_in, static_cast<uint32_t *>(dout), st);
+    }));
     *n_positions = npos;
     return PCX_OK;
 }

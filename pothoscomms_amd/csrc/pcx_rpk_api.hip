@@ -1,5 +1,5 @@
 // pcx_rpk_api.hip -- the pcx_repack handle (include/pcx.h): which conversion, the modulus and the bit order as they were set, the
-// group the reference reserves and how a call is cut.  The handle owns nothing on the device but its staging workspaces: a
+// group the reference reserves and how a call is cut.  The handle owns nothing on the device but the staging workspaces of host_call: a
 // process_dev call allocates nothing and walks its elements in slices of whole tiles, one launch each (repack.hip).
 #include "pcx_host.hpp"
 
@@ -14,11 +14,6 @@ struct pcx_repack {
 };
 
 namespace {
-bool disjoint(const void *in, size_t in_bytes, const void *out, size_t out_bytes)
-{
-    const char *a = static_cast<const char *>(in), *b = static_cast<const char *>(out);
-    return a + in_bytes <= b || b + out_bytes <= a;
-}
 // _reserveBytes (BytesToSymbols.cpp:69-76) and _reserveSyms (SymbolsToBytes.cpp:72-79); the bit kinds reserve one symbol's bits
 size_t group_in(const pcx_repack *h)
 {
@@ -34,19 +29,6 @@ const char *kind_name(int kind)
 {
     static const char *const names[] = {"bits to symbols", "symbols to bits", "bytes to symbols", "symbols to bytes"};
     return names[kind];
-}
-// the calls of one handle from host pointers: staged through the handle's workspaces, or in place on page-locked memory
-template <typename F>
-int host_call(pcx_repack *h, const void *in, size_t in_bytes, void *out, size_t out_bytes, F &&dev_call)
-{
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, out_bytes, h->wsOut));
-    PCX_TRY(stage_in(in, in_bytes, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, out_bytes, h->wsOut, &dout, &staged));
-    PCX_TRY(dev_call(din, dout, st));
-    return stage_out_end(out, out_bytes, h->wsOut, staged, st);
 }
 }  // namespace
 
@@ -111,7 +93,7 @@ int pcx_repack_process_dev(pcx_repack *h, const void *in_dev, void *out_dev, siz
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(n % group_in(h) == 0, "%s: %zu elements are not a whole group of %zu", kind_name(h->kind), n, group_in(h));
     PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
-    PCX_CHECK_ARG(disjoint(in_dev, n, out_dev, repack_out_elems(h->kind, h->mod, n)), "%s: out overlaps in", kind_name(h->kind));
+    PCX_CHECK_ARG(buffers_ok(in_dev, n, out_dev, repack_out_elems(h->kind, h->mod, n), false), "%s: out overlaps in", kind_name(h->kind));
     DeviceScope dev_scope(h->cx.device);
     hipStream_t st = as_stream(stream);
     PCX_TRY(ctx_enter(h->cx, st));
@@ -130,7 +112,7 @@ int pcx_repack_process(pcx_repack *h, const void *in, void *out, size_t n)
     PCX_CHECK_ARG(n % group_in(h) == 0, "%s: %zu elements are not a whole group of %zu", kind_name(h->kind), n, group_in(h));
     PCX_CHECK_ARG(in && out, "null buffer");
     const size_t m = repack_out_elems(h->kind, h->mod, n);
-    PCX_CHECK_ARG(disjoint(in, n, out, m), "%s: out overlaps in", kind_name(h->kind));
+    PCX_CHECK_ARG(buffers_ok(in, n, out, m, false), "%s: out overlaps in", kind_name(h->kind));
     DeviceScope dev_scope(h->cx.device);
     return host_call(h, in, n, out, m, [&](const void *din, void *dout, hipStream_t st) { return pcx_repack_process_dev(h, din, dout, n, st); });
 }

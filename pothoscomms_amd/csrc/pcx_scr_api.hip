@@ -172,9 +172,8 @@ int pcx_scrambler_get_state(pcx_scrambler *h, int64_t *data, int64_t *mask)
 {
     PCX_CHECK_ARG(h && data && mask, "null argument");
     DeviceScope dev_scope(h->cx.device);
-    PCX_TRY(ctx_quiesce(h->cx));
     uint64_t d = 0;
-    PCX_HIP(hipMemcpy(&d, h->state.p, sizeof(d), hipMemcpyDeviceToHost));
+    PCX_TRY(ctx_read_back(h->cx, &d, h->state.p, sizeof(d)));
     *data = (int64_t)d;
     *mask = (int64_t)h->p.mask;
     return PCX_OK;
@@ -187,9 +186,9 @@ int pcx_scrambler_process_dev(pcx_scrambler *h, const void *in_dev, void *out_de
     DeviceScope dev_scope(h->cx.device);
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    PCX_CHECK_ARG(buffers_ok(in_dev, n, out_dev, n, true), "scrambler: out overlaps in (in place means out == in)");
     const char *in = static_cast<const char *>(in_dev);
     char *out = static_cast<char *>(out_dev);
-    PCX_CHECK_ARG(in == out || in + n <= out || out + n <= in, "scrambler: out overlaps in (in place means out == in)");
     hipStream_t st = as_stream(stream);
     PCX_TRY(ctx_enter(h->cx, st));
     uint64_t *state = static_cast<uint64_t *>(h->state.p);
@@ -210,12 +209,5 @@ int pcx_scrambler_process(pcx_scrambler *h, const void *in, void *out, size_t n)
     DeviceScope dev_scope(h->cx.device);
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, n, h->wsOut));
-    PCX_TRY(stage_in(in, n, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, n, h->wsOut, &dout, &staged));
-    PCX_TRY(pcx_scrambler_process_dev(h, din, dout, n, st));
-    return stage_out_end(out, n, h->wsOut, staged, st);
+    return host_call(h, in, n, out, n, [&](const void *din, void *dout, hipStream_t st) { return pcx_scrambler_process_dev(h, din, dout, n, st); });
 }

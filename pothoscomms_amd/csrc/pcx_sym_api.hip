@@ -9,12 +9,6 @@
 using namespace pcx;
 
 namespace {
-bool device_reachable()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return n > 0;
-}
 // the value 1 of a stream type (the constructors' maps: SymbolMapper.cpp:58, SymbolSlicer.cpp:64)
 std::vector<unsigned char> one_element(int scalar, bool cplx)
 {
@@ -26,26 +20,6 @@ std::vector<unsigned char> one_element(int scalar, bool cplx)
     default: e[0] = 1;          // little-endian integers
     }
     return e;
-}
-// disjoint, or (where the element sizes agree) the same buffer
-bool overlap_ok(const void *in, size_t in_bytes, const void *out, size_t out_bytes, bool in_place)
-{
-    const char *a = static_cast<const char *>(in), *b = static_cast<const char *>(out);
-    if (in_place && a == b) return true;
-    return a + in_bytes <= b || b + out_bytes <= a;
-}
-// the calls of one handle from host pointers: staged through the handle's workspaces, or in place on page-locked memory
-template <typename H, typename F>
-int host_call(H *h, const void *in, size_t in_bytes, void *out, size_t out_bytes, F &&dev_call)
-{
-    hipStream_t st;
-    PCX_TRY(ctx_own_stream(h->cx, &st));
-    const void *din; void *dout; bool staged;
-    PCX_TRY(stage_reserve(out, out_bytes, h->wsOut));
-    PCX_TRY(stage_in(in, in_bytes, h->wsIn, st, &din));
-    PCX_TRY(stage_out_begin(out, out_bytes, h->wsOut, &dout, &staged));
-    PCX_TRY(dev_call(din, dout, st));
-    return stage_out_end(out, out_bytes, h->wsOut, staged, st);
 }
 }  // namespace
 
@@ -82,7 +56,7 @@ int pcx_mapper_create(int scalar, int is_complex, pcx_mapper **out)
     if (!h) { set_error("out of memory"); return PCX_ERR_STATE; }
     h->scalar = scalar;
     h->cplx = is_complex != 0;
-    h->es = (size_t)scalar_bytes(scalar) * (h->cplx ? 2 : 1);
+    h->es = elem_bytes(scalar, h->cplx);
     h->map = one_element(scalar, h->cplx);
     if (device_reachable()) {
         DeviceScope dev_scope(h->cx.device);
@@ -120,7 +94,7 @@ int pcx_mapper_process_dev(pcx_mapper *h, const void *in_dev, void *out_dev, siz
     PCX_CHECK_ARG(h, "null handle");
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
-    PCX_CHECK_ARG(overlap_ok(in_dev, n, out_dev, n * h->es, false), "symbol mapper: out overlaps in");
+    PCX_CHECK_ARG(buffers_ok(in_dev, n, out_dev, n * h->es, false), "symbol mapper: out overlaps in");
     DeviceScope dev_scope(h->cx.device);
     PCX_TRY(mapper_prepare(h));
     hipStream_t st = as_stream(stream);
@@ -138,7 +112,7 @@ int pcx_mapper_process(pcx_mapper *h, const void *in, void *out, size_t n)
     PCX_CHECK_ARG(h, "null handle");
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
-    PCX_CHECK_ARG(overlap_ok(in, n, out, n * h->es, false), "symbol mapper: out overlaps in");
+    PCX_CHECK_ARG(buffers_ok(in, n, out, n * h->es, false), "symbol mapper: out overlaps in");
     DeviceScope dev_scope(h->cx.device);
     return host_call(h, in, n, out, n * h->es,
                      [&](const void *din, void *dout, hipStream_t st) { return pcx_mapper_process_dev(h, din, dout, n, st); });
@@ -186,7 +160,7 @@ int pcx_slicer_create(int scalar, int is_complex, pcx_slicer **out)
     if (!h) { set_error("out of memory"); return PCX_ERR_STATE; }
     h->scalar = scalar;
     h->cplx = is_complex != 0;
-    h->es = (size_t)scalar_bytes(scalar) * (h->cplx ? 2 : 1);
+    h->es = elem_bytes(scalar, h->cplx);
     h->map = one_element(scalar, h->cplx);
     if (device_reachable()) {
         DeviceScope dev_scope(h->cx.device);
@@ -233,7 +207,7 @@ int pcx_slicer_process_dev(pcx_slicer *h, const void *in_dev, void *out_dev, siz
     PCX_CHECK_ARG(h, "null handle");
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
-    PCX_CHECK_ARG(overlap_ok(in_dev, n * h->es, out_dev, n, false), "symbol slicer: out overlaps in");
+    PCX_CHECK_ARG(buffers_ok(in_dev, n * h->es, out_dev, n, false), "symbol slicer: out overlaps in");
     DeviceScope dev_scope(h->cx.device);
     PCX_TRY(slicer_prepare(h));
     hipStream_t st = as_stream(stream);
@@ -251,7 +225,7 @@ int pcx_slicer_process(pcx_slicer *h, const void *in, void *out, size_t n)
     PCX_CHECK_ARG(h, "null handle");
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
-    PCX_CHECK_ARG(overlap_ok(in, n * h->es, out, n, false), "symbol slicer: out overlaps in");
+    PCX_CHECK_ARG(buffers_ok(in, n * h->es, out, n, false), "symbol slicer: out overlaps in");
     DeviceScope dev_scope(h->cx.device);
     return host_call(h, in, n * h->es, out, n,
                      [&](const void *din, void *dout, hipStream_t st) { return pcx_slicer_process_dev(h, din, dout, n, st); });
@@ -338,9 +312,8 @@ int pcx_diffcode_get_state(pcx_diffcode *h, unsigned char *last)
     *last = 0;
     if (!h->ready) return PCX_OK;
     DeviceScope dev_scope(h->cx.device);
-    PCX_TRY(ctx_quiesce(h->cx));
     uint32_t w = 0;
-    PCX_HIP(hipMemcpy(&w, h->state.p, sizeof(w), hipMemcpyDeviceToHost));
+    PCX_TRY(ctx_read_back(h->cx, &w, h->state.p, sizeof(w)));
     *last = (unsigned char)w;
     return PCX_OK;
 }
@@ -358,7 +331,7 @@ int pcx_diffcode_process_dev(pcx_diffcode *h, const void *in_dev, void *out_dev,
     PCX_CHECK_ARG(h, "null handle");
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
-    PCX_CHECK_ARG(overlap_ok(in_dev, n, out_dev, n, true), "differential coder: out overlaps in (in place means out == in)");
+    PCX_CHECK_ARG(buffers_ok(in_dev, n, out_dev, n, true), "differential coder: out overlaps in (in place means out == in)");
     DeviceScope dev_scope(h->cx.device);
     PCX_TRY(diff_prepare(h));
     hipStream_t st = as_stream(stream);
@@ -377,7 +350,7 @@ int pcx_diffcode_process(pcx_diffcode *h, const void *in, void *out, size_t n)
     PCX_CHECK_ARG(h, "null handle");
     if (n == 0) return PCX_OK;
     PCX_CHECK_ARG(in && out, "null buffer");
-    PCX_CHECK_ARG(overlap_ok(in, n, out, n, true), "differential coder: out overlaps in (in place means out == in)");
+    PCX_CHECK_ARG(buffers_ok(in, n, out, n, true), "differential coder: out overlaps in (in place means out == in)");
     DeviceScope dev_scope(h->cx.device);
     return host_call(h, in, n, out, n, [&](const void *din, void *dout, hipStream_t st) { return pcx_diffcode_process_dev(h, din, dout, n, st); });
 }

@@ -16,26 +16,9 @@ import numpy as np
 import pytest
 
 from pothoscomms_amd import _lib, device, taps as tp
-from tests.util import TOL, nerr
+from tests.util import TOL, Pinned, nerr
 
 pytestmark = pytest.mark.gpu
-
-
-class Pinned:
-    """a numpy array over a pcx_host_alloc slab"""
-
-    def __init__(self, shape, dtype):
-        self.L = _lib.load()
-        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        self.p = C.c_void_p()
-        _lib.check(self.L.pcx_host_alloc(C.byref(self.p), nbytes))
-        self.a = np.ctypeslib.as_array((C.c_char * nbytes).from_address(self.p.value)).view(dtype).reshape(shape)
-
-    def free(self):
-        if self.p:
-            self.a = None
-            _lib.check(self.L.pcx_host_free(self.p))
-            self.p = None
 
 
 def _fir_host(f, x, y, n_in, n_out_cap):

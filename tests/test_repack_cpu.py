@@ -283,6 +283,30 @@ def test_abi_argument_errors_come_before_any_device_call(pcx):
     assert L.pcx_repack_destroy(None) == 0
 
 
+def test_overlap_refusals_name_the_kind_and_come_before_any_device_call(pcx):
+    """The rule of in and out on fabricated addresses, which are never dereferenced: no kind works in place, so every shared byte is
+    refused -- the same buffer, out one element into in, one byte shared at either end -- with the kind's own text, by the host and
+    the device entry point alike."""
+    L, E = pcx._lib.load(), pcx._lib.ERR_ARG
+    err = pcx._lib.last_error
+    base = 1 << 40
+    texts = {"bits_to_symbols": "bits to symbols", "symbols_to_bits": "symbols to bits", "bytes_to_symbols": "bytes to symbols",
+             "symbols_to_bytes": "symbols to bytes"}
+    for ki, kind in enumerate(M.KINDS):
+        h = C.c_void_p()
+        assert L.pcx_repack_create(ki, C.byref(h)) == 0
+        try:
+            assert L.pcx_repack_set_modulus(h, 3) == 0
+            gin, gout = M.group(kind, 3)
+            nin, nout = (1 << 18) * gin, (1 << 18) * gout
+            text = texts[kind] + ": out overlaps in"
+            for out in (base, base + 1, base + nin - 1, base - nout + 1):
+                assert L.pcx_repack_process_dev(h, C.c_void_p(base), C.c_void_p(out), nin, None) == E and err() == text, (kind, out - base)
+                assert L.pcx_repack_process(h, C.c_void_p(base), C.c_void_p(out), nin) == E and err() == text, (kind, out - base)
+        finally:
+            assert L.pcx_repack_destroy(h) == 0
+
+
 def test_handle_reports_groups_and_geometry_at_every_setting(dev):
     for kind in M.KINDS:
         r = dev.SymbolRepacker(kind)

@@ -204,6 +204,36 @@ def test_abi_argument_errors_come_before_any_device_call(pcx):
             assert L.pcx_diffcode_destroy(h) == 0
 
 
+def test_overlap_refusals_name_the_block_and_come_before_any_device_call(pcx):
+    """The rule of in and out on fabricated addresses, which are never dereferenced: the mapper and the slicer refuse every shared byte,
+    out == in included (their element sizes differ); the coders refuse everything but out == in.  One byte shared at either end is
+    refused, with the handle's own text, by the host and the device entry point alike."""
+    L, E = pcx._lib.load(), pcx._lib.ERR_ARG
+    err = pcx._lib.last_error
+    base, n = 1 << 40, 1 << 20
+    for fam, text, nin, nout in (("pcx_mapper", "symbol mapper: out overlaps in", n, 16 * n), ("pcx_slicer", "symbol slicer: out overlaps in", 16 * n, n)):
+        f = lambda name: getattr(L, fam + "_" + name)      # noqa: E731
+        h = C.c_void_p()
+        assert f("create")(pcx.F64, 1, C.byref(h)) == 0
+        try:
+            # the same buffer, one input element in, the last byte of in, the last byte of out
+            for out in (base, base + nin // n, base + nin - 1, base - nout + 1):
+                assert f("process_dev")(h, C.c_void_p(base), C.c_void_p(out), n, None) == E and err() == text, (fam, out - base)
+                assert f("process")(h, C.c_void_p(base), C.c_void_p(out), n) == E and err() == text, (fam, out - base)
+        finally:
+            assert f("destroy")(h) == 0
+    text = "differential coder: out overlaps in (in place means out == in)"
+    for decode in (0, 1):
+        h = C.c_void_p()
+        assert L.pcx_diffcode_create(decode, C.byref(h)) == 0
+        try:
+            for out in (base + 1, base + n - 1, base - n + 1):
+                assert L.pcx_diffcode_process_dev(h, C.c_void_p(base), C.c_void_p(out), n, None) == E and err() == text, out - base
+                assert L.pcx_diffcode_process(h, C.c_void_p(base), C.c_void_p(out), n) == E and err() == text, out - base
+        finally:
+            assert L.pcx_diffcode_destroy(h) == 0
+
+
 def test_encoder_plan_of_the_handle_follows_the_table(dev):
     c = dev.DifferentialCoder()
     assert (c.symbols(), c.plan(), c.decode) == (2, dev._lib.DIFF_SCAN, False)

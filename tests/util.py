@@ -89,3 +89,23 @@ def bands_intact(whole, n_elems, width, fill, offset=0):
     if fill != fill:      # NaN poison
         return bool(lo.isnan().all()) and bool(hi.isnan().all())
     return bool((lo == fill).all()) and bool((hi == fill).all())
+
+
+class Pinned:
+    """a numpy array over a pcx_host_alloc slab"""
+
+    def __init__(self, shape, dtype):
+        import ctypes as C
+
+        from pothoscomms_amd import _lib
+        self._lib, self.L = _lib, _lib.load()
+        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        self.p = C.c_void_p()
+        _lib.check(self.L.pcx_host_alloc(C.byref(self.p), nbytes))
+        self.a = np.ctypeslib.as_array((C.c_char * nbytes).from_address(self.p.value)).view(dtype).reshape(shape)
+
+    def free(self):
+        if self.p:
+            self.a = None
+            self._lib.check(self.L.pcx_host_free(self.p))
+            self.p = None
