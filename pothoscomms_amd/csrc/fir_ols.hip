@@ -17,6 +17,8 @@
 // HBM traffic per block: 32 KiB read + 8*S bytes written; LDS: one padded 34 KiB image.
 // What bounds it: DESIGN.md 4.1 (profiles/r03/ols_lab3.md).
 #include "fft4096.hpp"
+#include "ols_block.hpp"
+#include "ols_geometry.hpp"
 #include "pcx_sched.hpp"
 #include <cstdio>
 #include <cstdlib>
@@ -178,10 +180,7 @@ __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_
         pass2<PART>(v, lds, j);
         pass3<PART>(v, lds, j, tw3);
         }
-        // spectrum times H, re-ordered into natural register order for the next pass 1.
-        // The inverse transform runs on the FORWARD passes: IFFT(z) = conj(FFT(conj(z))), so
-        // one set of twiddles serves both directions.  u = conj(v * H); the final conj rides
-        // on the last additions of the inverse's third pass.
+        // spectrum times H, re-ordered into natural register order for the next pass 1: u = conj(v * H) (ols_block.hpp)
         cf u[16];
         if (HGLOBAL) {
             const cf *Hp = reinterpret_cast<const cf *>(Hspec);
@@ -189,13 +188,7 @@ __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_
 #pragma unroll
             for (int k = 0; k < 16; k++) H[k] = Hp[j + 256 * k];
         }
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-            const int k0 = bin_of(q), k1 = bin_of(q + 1);
-            u[k0] = v[q];
-            u[k1] = v[q + 1];
-            cmul2_conj(u[k0], u[k1], H[k0], H[k1]);
-        }
+        spectrum_times_h(u, v, H);
         if (CHUNKED == 3) deal.publish(j);  // the inverse passes' barriers stand between this and deal.advance()
         // second half of a block ahead of other workgroups' first halves (priority, then age, decides VALU issue between the four
         // waves of a SIMD): blocks already half done retire -- and free their loads' successors -- sooner.  Measured +1.7 %
@@ -265,16 +258,9 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
         warned = true;
     }
 #endif
-    const size_t Km1 = K - 1;
-    const size_t Kov = align ? (Km1 + 15) / 16 * 16 : Km1;   // <= 2048
-    const size_t pad = Kov - Km1;
-    const size_t S = 4096 - Kov;
-    const size_t nblocks = (n_out + S - 1) / S;
     // full blocks: window inside the buffer and all S outputs wanted
-    const size_t first_full = pad > lead_valid ? 1 : 0;
-    size_t nfull = n_out / S;
-    while (nfull > first_full && (nfull - 1) * S - pad + 4096 > in_elems) nfull--;
-    if (nfull < first_full) nfull = first_full;
+    const OlsGeometry g = ols_geometry(K, align ? 16 : 1, 4096, n_out, in_elems, lead_valid);   // Kov <= 2048
+    const size_t Kov = g.Kov, pad = g.pad, nblocks = g.nblocks, first_full = g.first_full, nfull = g.nfull;
     const float2 *pi = (const float2 *)in, *ph = (const float2 *)Hspec, *pt = (const float2 *)tw4096;
     float2 *po = (float2 *)out;
     // slots below 128: a call on HOST memory over PCIe (pcx_api.hip host_grid): that many workgroups on the grid stride, several blocks each,
@@ -434,13 +420,7 @@ __global__ __launch_bounds__(256, 4) void fir_f32_ols4096_kernel(const float *__
         walk.draw(j);                       // behind the first butterflies (pcx_sched.hpp)
         dif_rest(v, lds, j);
         cf u[16];
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-            const int k0 = bin_of(q), k1 = bin_of(q + 1);
-            u[k0] = v[q];
-            u[k1] = v[q + 1];
-            cmul2_conj(u[k0], u[k1], H[k0], H[k1]);
-        }
+        spectrum_times_h(u, v, H);
         walk.publish(j);
         __builtin_amdgcn_s_setprio(1);      // as fir_cf32_ols4096_kernel: the second half of a block first
         dit_back(u, lds, j, tw3);           // conjugated on the last additions: u = the time samples
@@ -468,10 +448,8 @@ int launch_fir_f32_ols4096(const void *in, size_t in_elems, void *out, size_t n_
 {
     if (n_out == 0) return PCX_OK;
     if (K < 1 || K > 2049) { set_error("fir ols (real): K=%zu outside 1..2049", K); return PCX_ERR_UNSUPPORTED; }
-    const size_t Km1 = K - 1;
-    const size_t Kov = (Km1 + 31) / 32 * 32, pad = Kov - Km1;     // <= 2048
-    const size_t S = 4096 - Kov;
-    const size_t nblocks = (n_out + S - 1) / S;
+    const OlsGeometry g = ols_geometry(K, 32, 4096, n_out, in_elems, 0);     // Kov <= 2048
+    const size_t Kov = g.Kov, pad = g.pad, nblocks = g.nblocks;
     const size_t npairs = (nblocks + 1) / 2;
     const bool dyn = sched && npairs > 2 * 1024 && !PCX_ENV_SET("PCX_SCHED_STATIC");
     const unsigned grid = dyn ? 1024u : persistent_grid(npairs, 1024);
@@ -528,13 +506,7 @@ __global__ __launch_bounds__(256, 4) void fir_cf32_ols4096_poly_kernel(const flo
         dif_a_math(v, tw3);
         dif_rest(v, lds, j);
         cf u[16];
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-            const int k0 = bin_of(q), k1 = bin_of(q + 1);
-            u[k0] = v[q];
-            u[k1] = v[q + 1];
-            cmul2_conj(u[k0], u[k1], H[k0], H[k1]);
-        }
+        spectrum_times_h(u, v, H);
         dit_back(u, lds, j, tw3);           // conjugated on the last additions: u = the time samples
         // input index of time sample i is n = b*S + i - (K-1); flat index f = n*L + jrow
         const unsigned long long B0 = (unsigned long long)(b * S) * L + jrow + 1;   // f+1 at i' = i-(K-1) = 0 (wave-uniform)
@@ -694,13 +666,7 @@ __global__ __launch_bounds__(256, OCC) void fmchain_cf32_ols4096_kernel(const fl
         if (DYN) deal.draw(j);              // behind the first butterflies (pcx_sched.hpp)
         dif_rest(v, lds, j);
         cf u[16];
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-            const int k0 = bin_of(q), k1 = bin_of(q + 1);
-            u[k0] = v[q];
-            u[k1] = v[q + 1];
-            cmul2_conj(u[k0], u[k1], H[k0], H[k1]);
-        }
+        spectrum_times_h(u, v, H);
         if (DYN) deal.publish(j);
         __builtin_amdgcn_s_setprio(1);      // as fir_cf32_ols4096_kernel: the second half of a block first
         dit_back<false>(u, lds, j, tw3);
@@ -831,9 +797,9 @@ int launch_fmchain_cf32_ols4096(const void *in, size_t in_elems, void *out, size
     if (K < 1 || K > 2048) { set_error("fm chain ols: K=%zu outside 1..2048", K); return PCX_ERR_UNSUPPORTED; }
     // PCX_FMCHAIN_OCC (libpcx_hip_diag.so only, A/B): 3 = 3 workgroups per CU, 5 = 4 per CU with plain loads/stores; default 4 + row policy
     const int occ = (int)PCX_ENV_INT("PCX_FMCHAIN_OCC", 4);
-    const size_t Kov = (K + 31) / 32 * 32, pad = Kov - K;    // <= 2048
-    const size_t S = 4096 - Kov;
-    const size_t nblocks = (n_out + S - 1) / S;
+    // the blocks overlap by K samples (the FIR's K-1 and the demodulator's one): the geometry of K + 1 taps
+    const OlsGeometry g = ols_geometry(K + 1, 32, 4096, n_out, in_elems, 0);    // Kov <= 2048
+    const size_t Kov = g.Kov, pad = g.pad, S = g.S, nblocks = g.nblocks;
     const bool host_grid = slots > 0 && slots < 128;      // a call on host memory over PCIe: few workgroups, several blocks each (launch_fir_cf32_ols4096)
     if (!host_grid && (slots < 128 || slots > 1024 || slots % 128)) slots = 1024;
     const bool dyn = !host_grid && sched && nblocks > 2 * (size_t)slots && !PCX_ENV_SET("PCX_SCHED_STATIC");   // dynamic dealing when the handle brought its counter pair and the launch is long

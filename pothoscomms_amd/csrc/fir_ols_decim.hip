@@ -17,6 +17,8 @@
 // H on the host (pcx_api.hip) together with the 1/N of the inverse.  Block geometry as in fir_ols.hip: overlap Kov =
 // K-1 rounded up to 16 samples (a multiple of every M here), S = 4096 - Kov full-rate outputs = S/M stored per block.
 #include "fft4096.hpp"
+#include "ols_block.hpp"
+#include "ols_geometry.hpp"
 #include "pcx_sched.hpp"
 #include <cstdlib>
 
@@ -57,15 +59,8 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_decim_kernel(const 
     // the lane's 16 bins of H are re-read from L2 at the multiply (not held in 32 VGPRs): the 256-point stage keeps a
     // second 16-point set alive across two barriers and the kernel has to stay within 128 VGPRs for 4 workgroups per CU
     const cf *Hg = reinterpret_cast<const cf *>(Hspec) + j;
-    // W_{N/M}^j: the lane constant of the decimation-in-frequency stage (its powers k1 = 2 .. P-1 are rebuilt by
-    // multiplication in every block: 6 packed multiplies against 12 more registers)
-    cf td1;
-    {
-        float sn, cs;
-        sincospif(-2.0f * (float)spec_lane(j) / (float)(256 * P), &sn, &cs);    // the lane's bins are js + 256 r (file header)
-        td1 = cf{cs, sn};
-    }
-    const int js = spec_lane(j);
+    const int js = spec_lane(j);                     // the lane's bins are js + 256 r (file header)
+    const cf td1 = radix_stage_twiddle<P>(js);       // W_{N/M}^js: the lane constant of the decimation-in-frequency stage
     const int fi = j >> 4, l = j & 15;               // sub-frame and lane inside it (lanes j < 16 P run the 256-point stage)
     const bool sub = j < 16 * P;
 
@@ -108,13 +103,7 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_decim_kernel(const 
         const cf *Hb = Hg;
         asm volatile("" : "+v"(Hb));   // loop-invariant: without this the loads are hoisted back into registers
         cf u[16];
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-            const int k0 = bin_of(q), k1 = bin_of(q + 1);
-            u[k0] = v[q];
-            u[k1] = v[q + 1];
-            cmul2_conj(u[k0], u[k1], Hb[256 * k0], Hb[256 * k1]);
-        }
+        spectrum_times_h_l2(u, v, Hb);
         // fold: the M bins that alias onto k' = j + 256 r'
         cf z[P];
 #pragma unroll
@@ -124,17 +113,7 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_decim_kernel(const 
             for (int m = 1; m < M; m++) z[r] = z[r] + u[r + P * m];
         }
         // radix-P decimation-in-frequency stage over r', then the lane twiddle W^(j k1)
-        if constexpr (P == 8) fft8(z[0], z[1], z[2], z[3], z[4], z[5], z[6], z[7]);
-        else if constexpr (P == 4) fft4(z[0], z[1], z[2], z[3]);
-        else if constexpr (P == 2) { const cf a = z[0], c = z[1]; z[0] = a + c; z[1] = a - c; }
-        {
-            cf t = td1;
-#pragma unroll
-            for (int k1 = 1; k1 < P; k1++) {
-                z[k1] = cmul1(z[k1], t);
-                if (k1 + 1 < P) t = cmul1(t, td1);
-            }
-        }
+        radix_stage_dif<P>(z, td1);
         __syncthreads();                                  // every lane is done with the forward image (pass 3 reads)
         if (NOINV) {
 #pragma unroll
@@ -286,12 +265,7 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_decim_batched_kerne
 #pragma unroll
         for (int k = 0; k < 16; k++) Hr[k] = Hg[256 * k];
     }
-    cf td1;
-    {
-        float sn, cs;
-        sincospif(-2.0f * (float)js / (float)(256 * P), &sn, &cs);
-        td1 = cf{cs, sn};
-    }
+    const cf td1 = radix_stage_twiddle<P>(js);
     const int fi = j >> 4, l = j & 15;               // sub-transform t = fi (block fi / P of the group, k1 = fi % P) and lane inside it
     const bool sub = j < 16 * T;
 
@@ -343,14 +317,8 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_decim_batched_kerne
             const cf *Hb = Hg;
             asm volatile("" : "+v"(Hb));
             cf u[16];
-#pragma unroll
-            for (int q = 0; q < 16; q += 2) {
-                const int k0 = bin_of(q), k1 = bin_of(q + 1);
-                u[k0] = v[q];
-                u[k1] = v[q + 1];
-                if (HREG) cmul2_conj(u[k0], u[k1], Hr[k0], Hr[k1]);
-                else cmul2_conj(u[k0], u[k1], Hb[256 * k0], Hb[256 * k1]);
-            }
+            if (HREG) spectrum_times_h(u, v, Hr);
+            else spectrum_times_h_l2(u, v, Hb);
             cf z[P];
 #pragma unroll
             for (int r = 0; r < P; r++) {
@@ -358,17 +326,7 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_decim_batched_kerne
 #pragma unroll
                 for (int m = 1; m < M; m++) z[r] = z[r] + u[r + P * m];
             }
-            if constexpr (P == 8) fft8(z[0], z[1], z[2], z[3], z[4], z[5], z[6], z[7]);
-            else if constexpr (P == 4) fft4(z[0], z[1], z[2], z[3]);
-            else if constexpr (P == 2) { const cf a = z[0], c = z[1]; z[0] = a + c; z[1] = a - c; }
-            {
-                cf t = td1;
-#pragma unroll
-                for (int k1 = 1; k1 < P; k1++) {
-                    z[k1] = cmul1(z[k1], t);
-                    if (k1 + 1 < P) t = cmul1(t, td1);
-                }
-            }
+            radix_stage_dif<P>(z, td1);
 #pragma unroll
             for (int k1 = 0; k1 < P; k1++) zz[g * P + k1] = z[k1];
         }
@@ -437,15 +395,10 @@ int launch_decim(const void *in, size_t in_elems, void *out, size_t n_iter, cons
                  void *sched, hipStream_t st)
 {
     constexpr size_t M = (size_t)1 << LOG2M;
-    const size_t Km1 = K - 1;
-    const size_t Kov = (Km1 + 15) / 16 * 16, pad = Kov - Km1;
-    const size_t S = 4096 - Kov, Sd = S / M;
     const size_t n_out = n_iter / M;
-    const size_t nblocks = (n_out + Sd - 1) / Sd;
-    const size_t first_full = pad > 0 ? 1 : 0;
-    size_t nfull = n_iter / S;
-    while (nfull > first_full && (nfull - 1) * S - pad + 4096 > in_elems) nfull--;
-    if (nfull < first_full) nfull = first_full;
+    // blocks of S full-rate outputs = S / M stored ones (Kov is a multiple of every M here)
+    const OlsGeometry g = ols_geometry(K, 16, 4096, n_out * M, in_elems, 0);
+    const size_t Kov = g.Kov, pad = g.pad, nblocks = g.nblocks, first_full = g.first_full, nfull = g.nfull;
     // dynamic dealing measured SLOWER here (tools/ab_sched.sh, M = 8: 0.2190 vs 0.1950 ms): the kernel is bound by its arithmetic and
     // re-reads H per block, and the grid stride keeps neighbouring blocks on neighbouring workgroups.  The product keeps the
     // stride; PCX_SCHED_RESAMPLERS (diagnostic library) selects the dealer for A/B.
@@ -574,13 +527,8 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_interp_kernel(const
 #pragma unroll
         for (int k = 0; k < 16; k++) Hr[k] = Hg[256 * k];
     }
-    cf td1;
-    {
-        float sn, cs;
-        sincospif(-2.0f * (float)spec_lane(j) / (float)ND, &sn, &cs);     // the lane takes the bins js + 256 r (decimator above)
-        td1 = cf{cs, sn};
-    }
-    const int js = spec_lane(j);
+    const int js = spec_lane(j);                     // the lane takes the bins js + 256 r (decimator above)
+    const cf td1 = radix_stage_twiddle<P>(js);
     const int fi = j >> 4, l = j & 15;
     const bool sub = j < 16 * P;
 
@@ -661,13 +609,8 @@ __global__ __launch_bounds__(256, OCC) void fir_cf32_ols4096_interp_kernel(const
         const cf *Hb = Hg;
         asm volatile("" : "+v"(Hb));
         cf u[16];
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-            u[r] = g[r & (P - 1)];
-            u[r + 1] = g[(r + 1) & (P - 1)];
-            if (HREG) cmul2_conj(u[r], u[r + 1], Hr[r], Hr[r + 1]);
-            else cmul2_conj(u[r], u[r + 1], Hb[256 * r], Hb[256 * (r + 1)]);
-        }
+        if (HREG) replicated_times_h<P>(u, g, Hr);
+        else replicated_times_h_l2<P>(u, g, Hb);
         walk.publish(j);                                  // two barriers follow
         lds_barrier();                                    // every lane has read its frame values: the inverse below reuses the image
         dit_back(u, lds, j, tw3);           // conjugated on the last additions: u = the time samples
@@ -714,13 +657,8 @@ __global__ __launch_bounds__(256, 3) void fir_cf32_ols4096_interp_batched_kernel
 #pragma unroll
         for (int k = 0; k < 16; k++) Hr[k] = Hg[256 * k];
     }
-    cf td1;
-    {
-        float sn, cs;
-        sincospif(-2.0f * (float)spec_lane(j) / (float)ND, &sn, &cs);     // the lane takes the bins js + 256 r (decimator above)
-        td1 = cf{cs, sn};
-    }
-    const int js = spec_lane(j);
+    const int js = spec_lane(j);                     // the lane takes the bins js + 256 r (decimator above)
+    const cf td1 = radix_stage_twiddle<P>(js);
     const int fi = j >> 4, l = j & 15;
     const bool sub = j < 16 * T;
 
@@ -813,13 +751,8 @@ __global__ __launch_bounds__(256, 3) void fir_cf32_ols4096_interp_batched_kernel
             const cf *Hb = Hg;
             asm volatile("" : "+v"(Hb));
             cf u[16];
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                u[r] = gv[r & (P - 1)];
-                u[r + 1] = gv[(r + 1) & (P - 1)];
-                if (HREG) cmul2_conj(u[r], u[r + 1], Hr[r], Hr[r + 1]);
-                else cmul2_conj(u[r], u[r + 1], Hb[256 * r], Hb[256 * (r + 1)]);
-            }
+            if (HREG) replicated_times_h<P>(u, gv, Hr);
+            else replicated_times_h_l2<P>(u, gv, Hb);
             lds_barrier();                                // every lane has parked its values / read the previous block's samples: the image is reused
             dit_back(u, lds, j, tw3);           // conjugated on the last additions: u = the time samples
             const size_t room = n_out - b * S_out;

@@ -19,6 +19,7 @@
 // issues one instruction per ~3.9 clocks and SIMD at the two waves per SIMD the 64 KB image allows (tools/f64_lab.hip): the
 // complex_int16 kernel runs at 0.9 of that rate (250 Gsamples/s at 255 taps).
 #include "fft_f64.hpp"
+#include "ols_geometry.hpp"
 #include <cstdio>
 #include <cstdlib>
 
@@ -265,16 +266,9 @@ template <int LOG2N, int IO>
 int launch_ols(const void *in, size_t in_elems, void *out, size_t n_out, const void *Hspec, size_t K, const void *tw, size_t M, QShift qs, hipStream_t st)
 {
     typedef OlsPlan<LOG2N> P;
-    const size_t Km1 = K - 1;
-    const size_t Kov = (Km1 + 15) / 16 * 16;
+    const OlsGeometry g = ols_geometry(K, 16, P::N, n_out, in_elems, 0);
+    const size_t Kov = g.Kov, pad = g.pad, nblocks = g.nblocks, first_full = g.first_full, nfull = g.nfull;
     if (Kov > (size_t)P::N / 2) { set_error("fir ols f64: K=%zu too long for %d-sample blocks", K, P::N); return PCX_ERR_UNSUPPORTED; }
-    const size_t pad = Kov - Km1;
-    const size_t S = P::N - Kov;
-    const size_t nblocks = (n_out + S - 1) / S;
-    const size_t first_full = pad > 0 ? 1 : 0;
-    size_t nfull = n_out / S;
-    while (nfull > first_full && (nfull - 1) * S - pad + P::N > in_elems) nfull--;
-    if (nfull < first_full) nfull = first_full;
     const size_t lds = (size_t)(P::LDS_IMG + P::LDS_T2) * sizeof(cd);
     auto k = M > 1 ? fir_cf64_ols_kernel<LOG2N, IO, true> : fir_cf64_ols_kernel<LOG2N, IO, false>;
     const unsigned magic = M > 1 ? (unsigned)(((1ull << 32) + M - 1) / M) : 0u;
@@ -464,12 +458,9 @@ template <int LOG2N, int IO>
 int launch_real_ols(const void *in, size_t in_elems, void *out, size_t n_out, const void *Hspec, size_t K, const void *tw, size_t M, QShift qs, hipStream_t st)
 {
     typedef OlsPlan<LOG2N> P;
-    const size_t Km1 = K - 1;
-    const size_t Kov = (Km1 + 15) / 16 * 16;
+    const OlsGeometry g = ols_geometry(K, 16, P::N, n_out, in_elems, 0);
+    const size_t Kov = g.Kov, pad = g.pad, nblocks_real = g.nblocks;
     if (Kov > (size_t)P::N / 2) { set_error("fir ols (real): K=%zu too long for %d-sample blocks", K, P::N); return PCX_ERR_UNSUPPORTED; }
-    const size_t pad = Kov - Km1;
-    const size_t S = P::N - Kov;
-    const size_t nblocks_real = (n_out + S - 1) / S;
     const size_t nblocks = (nblocks_real + 1) / 2;
     const size_t lds = (size_t)(P::LDS_IMG + P::LDS_T2) * sizeof(cd);
     auto k = M > 1 ? fir_real_ols_kernel<LOG2N, IO, true> : fir_real_ols_kernel<LOG2N, IO, false>;
@@ -723,12 +714,9 @@ template <int IO>
 int launch_ip(const void *in, size_t in_elems, void *out, size_t n_out, const void *Hspec, size_t K, const void *tw, size_t M, QShift qs, void *sched,
               hipStream_t st)
 {
-    const size_t Km1 = K - 1;
-    const size_t Kov = (Km1 + 15) / 16 * 16;
+    const OlsGeometry g = ols_geometry(K, 16, 4096, n_out, in_elems, 0);
+    const size_t Kov = g.Kov, pad = g.pad, nblocks = g.nblocks;
     if (Kov > 2048) { set_error("fir ols f64: K=%zu too long for 4096-sample blocks", K); return PCX_ERR_UNSUPPORTED; }
-    const size_t pad = Kov - Km1;
-    const size_t S = 4096 - Kov;
-    const size_t nblocks = (n_out + S - 1) / S;
     const size_t lds = (size_t)ip4096::kLdsSlots * sizeof(cd);
     const bool floorq = IO == 0 || (qs.mode == PCX_Q_FLOOR && qs.shift == (IO == 1 ? 16 : 8));
     // dealt from 512 persistent workgroups when the call is long enough for it to matter and nothing asks for a small grid (a
@@ -863,12 +851,9 @@ template <int IO>
 int launch_real_ip(const void *in, size_t in_elems, void *out, size_t n_out, const void *Hspec, size_t K, const void *tw, size_t M, QShift qs, void *sched,
                    hipStream_t st)
 {
-    const size_t Km1 = K - 1;
-    const size_t Kov = (Km1 + 15) / 16 * 16;
+    const OlsGeometry g = ols_geometry(K, 16, 4096, n_out, in_elems, 0);
+    const size_t Kov = g.Kov, pad = g.pad, nblocks_real = g.nblocks;
     if (Kov > 2048) { set_error("fir ols (real): K=%zu too long for 4096-sample blocks", K); return PCX_ERR_UNSUPPORTED; }
-    const size_t pad = Kov - Km1;
-    const size_t S = 4096 - Kov;
-    const size_t nblocks_real = (n_out + S - 1) / S;
     const size_t nblocks = (nblocks_real + 1) / 2;
     const size_t lds = (size_t)ip4096::kLdsSlots * sizeof(cd);
     const bool dyn = sched && M == 1 && nblocks > 4 * 512 && nblocks < ((size_t)1 << 31) && !g_link_grid && !PCX_ENV_SET("PCX_SCHED_STATIC");

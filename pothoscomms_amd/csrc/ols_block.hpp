@@ -1,0 +1,92 @@
+// ols_block.hpp -- the steps that the overlap-save /comms/fir_filter kernels on the 4096-point float32 transform share
+// (fir_ols.hip, fir_ols_decim.hip): one copy of each, inlined into every kernel that takes it.  Include after fft4096.hpp.
+//
+// What is here are the steps that live in registers: the spectrum multiply and the lane's part of the resampling kernels'
+// short transform.  Every kernel that calls one compiles to the instructions it had with the step written out.  The steps
+// around a memory access -- the window fetch, the 256-point sub-transforms through LDS, the row stores -- do NOT: taken out of
+// a kernel into a function they come back with another register assignment and another instruction order (what their unrolled
+// loops hold that does not change from block to block -- row tests, row offsets, descriptor bases -- is hoisted to another place
+// in the kernel's prologue), in kernels that are a few registers from spilling.  Those stay written out where they are.
+// The `asm volatile("" : "+v"(..))` / "+s" pins that keep a loop-invariant load inside a kernel's block loop are decisions of
+// that kernel and stay at its call site: these functions take the pinned pointer.
+#pragma once
+#include "fft4096.hpp"
+
+namespace pcx {
+namespace fft4k {
+
+// ---- spectrum times H ----
+// v[q] = X[.. + 256 bin_of(q)] as the forward passes leave it; u[r] = conj(X * H) in natural register order r for the first
+// pass of the inverse.  The inverse transform runs on the FORWARD passes: IFFT(z) = conj(FFT(conj(z))), so one set of twiddles
+// serves both directions; the final conj rides on the last additions of the inverse's third pass.
+// H: the lane's sixteen bins held in registers
+__device__ __forceinline__ void spectrum_times_h(cf (&u)[16], const cf (&v)[16], const cf (&H)[16])
+{
+#pragma unroll
+    for (int q = 0; q < 16; q += 2) {
+        const int k0 = bin_of(q), k1 = bin_of(q + 1);
+        u[k0] = v[q];
+        u[k1] = v[q + 1];
+        cmul2_conj(u[k0], u[k1], H[k0], H[k1]);
+    }
+}
+// Hb: the lane's bin 0 in the spectrum, the others 256 elements apart -- re-read from L2 in every block
+__device__ __forceinline__ void spectrum_times_h_l2(cf (&u)[16], const cf (&v)[16], const cf *Hb)
+{
+#pragma unroll
+    for (int q = 0; q < 16; q += 2) {
+        const int k0 = bin_of(q), k1 = bin_of(q + 1);
+        u[k0] = v[q];
+        u[k1] = v[q + 1];
+        cmul2_conj(u[k0], u[k1], Hb[256 * k0], Hb[256 * k1]);
+    }
+}
+// the interpolators: zero-stuffing by 16/P replicates the 256 P-point spectrum g, u[r] = conj(g[r mod P] * H[r])
+template <int P>
+__device__ __forceinline__ void replicated_times_h(cf (&u)[16], const cf (&g)[P], const cf (&H)[16])
+{
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        u[r] = g[r & (P - 1)];
+        u[r + 1] = g[(r + 1) & (P - 1)];
+        cmul2_conj(u[r], u[r + 1], H[r], H[r + 1]);
+    }
+}
+template <int P>
+__device__ __forceinline__ void replicated_times_h_l2(cf (&u)[16], const cf (&g)[P], const cf *Hb)
+{
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        u[r] = g[r & (P - 1)];
+        u[r + 1] = g[(r + 1) & (P - 1)];
+        cmul2_conj(u[r], u[r + 1], Hb[256 * r], Hb[256 * (r + 1)]);
+    }
+}
+
+// ---- the lane's part of the 256 P-point transform of the resampling kernels ----
+// W_{256 P}^js: the lane constant of the radix-P stage, js = spec_lane(j): the lane's bins are js + 256 r.  Its powers
+// 2 .. P-1 are rebuilt by multiplication in every block: 6 packed multiplies against 12 more registers.
+template <int P>
+__device__ __forceinline__ cf radix_stage_twiddle(int js)
+{
+    float sn, cs;
+    sincospif(-2.0f * (float)js / (float)(256 * P), &sn, &cs);
+    return cf{cs, sn};
+}
+// the decimators: radix-P decimation-in-frequency stage over the lane's P folded values, then the lane twiddle td1^k1 on value k1
+template <int P>
+__device__ __forceinline__ void radix_stage_dif(cf (&z)[P], cf td1)
+{
+    if constexpr (P == 8) fft8(z[0], z[1], z[2], z[3], z[4], z[5], z[6], z[7]);
+    else if constexpr (P == 4) fft4(z[0], z[1], z[2], z[3]);
+    else if constexpr (P == 2) { const cf a = z[0], c = z[1]; z[0] = a + c; z[1] = a - c; }
+    cf t = td1;
+#pragma unroll
+    for (int k1 = 1; k1 < P; k1++) {
+        z[k1] = cmul1(z[k1], t);
+        if (k1 + 1 < P) t = cmul1(t, td1);
+    }
+}
+
+}  // namespace fft4k
+}  // namespace pcx

@@ -47,6 +47,8 @@ PLANS = [
     # -- complex_float32 decimating: the folded spectrum (have_decim) for M = 2 and 4 / 8 / 16-fold, the strided polyphase kernel else --
     R("cf32 decim M=2", "complex_float32", "COMPLEX", 63, M=2),
     R("cf32 decim M=4", "complex_float32", "REAL", 100, M=4),
+    R("cf32 decim M=8", "complex_float32", "COMPLEX", 255, M=8),
+    R("cf32 decim M=8 K=2049", "complex_float32", "COMPLEX", 2049, M=8),
     R("cf32 decim M=16", "complex_float32", "COMPLEX", 255, M=16),
     R("cf32 decim M=160 (16-fold, one in 10 stored)", "complex_float32", "COMPLEX", 1000, M=160),
     R("cf32 poly strided M=3", "complex_float32", "COMPLEX", 100, M=3),

@@ -9,12 +9,12 @@ C = "pothoscomms_amd/csrc/"
 # the kernel each workload's PMC run measured and the source files it is built from: bench.py reports `traffic` only while
 # these files still hash to what they did when the measurement was filed (run this script on the tree the GPU run used)
 KERNELS = {
-    "fir255": ("fir_cf32_ols4096_kernel", [C + "fir_ols.hip", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
-    "fmchain": ("fmchain_cf32_ols4096_kernel", [C + "fir_ols.hip", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
+    "fir255": ("fir_cf32_ols4096_kernel", [C + "fir_ols.hip", C + "ols_block.hpp", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
+    "fmchain": ("fmchain_cf32_ols4096_kernel", [C + "fir_ols.hip", C + "ols_block.hpp", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
     "fft4096": ("fft_r16_kernel", [C + "fft_r16.hip", C + "fft4096.hpp"]),
     "direct255": ("fir_cf32_direct_kernel", [C + "fir_direct.hip"]),
-    "decim8": ("fir_cf32_ols4096_decim_batched_kernel", [C + "fir_ols_decim.hip", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
-    "interp4": ("fir_cf32_ols4096_interp_batched_kernel", [C + "fir_ols_decim.hip", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
+    "decim8": ("fir_cf32_ols4096_decim_batched_kernel", [C + "fir_ols_decim.hip", C + "ols_block.hpp", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
+    "interp4": ("fir_cf32_ols4096_interp_batched_kernel", [C + "fir_ols_decim.hip", C + "ols_block.hpp", C + "fft4096.hpp", C + "pcx_sched.hpp"]),
     "fir255_i16": ("fir_cf64_ip_kernel", [C + "fir_ols_f64.hip", C + "fft_f64.hpp", C + "pcx_sched.hpp"]),
     "fir4097": ("fir_cf32_upols_kernel", [C + "fir_ols_part.hip", C + "fft4096.hpp"]),
     "fir8193": ("fir_cf32_upols_kernel", [C + "fir_ols_part.hip", C + "fft4096.hpp"]),
