@@ -586,6 +586,69 @@ PCX_API int pcx_repack_process(pcx_repack *h, const void *in, void *out, size_t 
 PCX_API int pcx_repack_process_dev(pcx_repack *h, const void *in_dev, void *out_dev, size_t n, void *stream);
 
 /* ===================================================================== *
+ *  /comms/waveform_source, /comms/noise_source   (waveform/)
+ *
+ *  The two blocks that produce a stream.  Both walk a table of the output type cyclically from a carried index
+ *  (WaveformSource.cpp:98-108, NoiseSource.cpp:109-117): out[i] = table[(index + i * step) & (entries - 1)], the arithmetic modulo
+ *  2^64 as the reference's size_t is (a negative frequency is a huge step).  Every output is a table entry, so it is the reference's
+ *  bit for bit.  pcx_source is that walk on the device; the tables are built on the host by pcx_waveform_table and pcx_noise_table,
+ *  which restate updateTable() of the two blocks and need no device.
+ * ===================================================================== */
+typedef struct pcx_source pcx_source;
+/* A source of elements of (scalar, is_complex): any of the twelve stream types, an element of 1 to 16 bytes.  No table yet: generate
+ * is PCX_ERR_STATE until set_table.  The carried index starts at 0. */
+PCX_API int pcx_source_create(int scalar, int is_complex, pcx_source **out);
+PCX_API int pcx_source_destroy(pcx_source *h);
+/* The table (`entries` elements in the stream type's layout, copied) and the step of the walk.  entries must be a power of two of at
+ * most 2^20 (PCX_ERR_ARG "table size must be a power of two of at most 1048576 entries"), checked after the handle and before the
+ * table pointer.  The carried index is kept: it enters the new table as _index does after setFrequency. */
+PCX_API int pcx_source_set_table(pcx_source *h, const void *table, size_t entries, uint64_t step);
+PCX_API int pcx_source_get_index(const pcx_source *h, uint64_t *index);
+PCX_API int pcx_source_set_index(pcx_source *h, uint64_t index);
+/* tile: the elements one workgroup writes per pass (16 KiB of output); period: entries / gcd(step mod entries, entries), after how
+ * many elements the stream repeats (0 while there is no table); staged: whether that period is held in LDS (else read from global
+ * memory) */
+PCX_API int pcx_source_get_geometry(const pcx_source *h, size_t *tile, size_t *period, int *staged);
+/* The next n elements.  Checked in this order: the handle, n == 0 (nothing to do: PCX_OK, the index stays), the buffer, the table.
+ * generate writes host, page-locked or device memory and returns with the elements in `out`.  generate_dev only enqueues: it
+ * synchronises nothing and allocates nothing once a table is set, so it can be captured into a graph.  THE CARRIED INDEX IS HOST
+ * STATE: it advances by n * step when the call is MADE, not when it runs, so a captured call replays the window it was captured
+ * with, every time, and the index moves on by one window per capture and by none per replay.  That holds while the handle's
+ * settings stand: the graph reads the handle's device copy of one period of the walk, which the first generate call after a
+ * set_table, or after a set_index on a walk whose step is not 1, writes again in place (replays then emit windows of the NEW
+ * period), and which a set_table with a longer period reallocates (the graph then reads freed memory: capture again after any
+ * set_table).  n is a size_t, every index in the kernels is 64-bit, `out` may have any alignment the element type allows. */
+PCX_API int pcx_source_generate(pcx_source *h, void *out, size_t n);
+PCX_API int pcx_source_generate_dev(pcx_source *h, void *out_dev, size_t n, void *stream);
+
+/* updateTable() and setElem() of the waveform source (WaveformSource.cpp:178-259) on the host, in double and in the reference's
+ * order: the table size doubles from 4096 up to 2^20 while |llround(frac * size)| < 16, frac = (res == 0 ? freq : res) / rate;
+ * *step = size_t(llround(freq / rate * size)); entry i is Type(ampl * wave(i) + offset), real types taking the real part and
+ * integers converting by C++ truncation; wave is PCX_WAVE_CONST 1, PCX_WAVE_SINE std::polar(1.0, 2 pi i / size), PCX_WAVE_RAMP and
+ * PCX_WAVE_SQUARE with the quadrature component at (i + 3 size / 4) % size.
+ * table == NULL or cap == 0 only computes *entries and *step; else cap (elements) below *entries is PCX_ERR_ARG.
+ * An unknown wave is PCX_ERR_ARG "unknown waveform setting", a step of 0 at freq != 0 PCX_ERR_ARG "step size not achievable". */
+enum { PCX_WAVE_CONST = 0, PCX_WAVE_SINE = 1, PCX_WAVE_RAMP = 2, PCX_WAVE_SQUARE = 3 };
+PCX_API int pcx_waveform_table(int scalar, int is_complex, int wave, double rate, double freq, double res, double ampl_re, double ampl_im,
+                               double offset_re, double offset_im, void *table, size_t cap, size_t *entries, uint64_t *step);
+
+/* The generator of the noise source: a std::mt19937 and the four distributions as NoiseSource.cpp:188-250 calls them, on the host.
+ * use_seed == 0 seeds from std::random_device as the reference's constructor does; else from `seed`.
+ * pcx_noise_table fills the PCX_NOISE_ENTRIES entries Type(ampl * complex(a, b) + offset), b drawn BEFORE a (the reference leaves the
+ * order to its compiler; built with g++ it draws the imaginary component first: tests/golden/make_source_golden.py records it): PCX_NOISE_UNIFORM over [mean - b, mean + b), PCX_NOISE_NORMAL
+ * (mean, b), PCX_NOISE_LAPLACE from the uniform distribution AS IT WAS LAST SET (the reference's LAPLACE branch sets it to
+ * [mean - b, mean + b) and takes mean -+ b log(1 -+ u)), PCX_NOISE_POISSON (mean).  An unknown wave is PCX_ERR_ARG
+ * "unknown waveform setting".  pcx_noise_next_offset is the draw of every work(): uniform_int_distribution<size_t>(0, 4095). */
+typedef struct pcx_noise pcx_noise;
+enum { PCX_NOISE_UNIFORM = 0, PCX_NOISE_NORMAL = 1, PCX_NOISE_LAPLACE = 2, PCX_NOISE_POISSON = 3 };
+#define PCX_NOISE_ENTRIES 4096
+PCX_API int pcx_noise_create(int use_seed, uint32_t seed, pcx_noise **out);
+PCX_API int pcx_noise_destroy(pcx_noise *h);
+PCX_API int pcx_noise_table(pcx_noise *h, int scalar, int is_complex, int wave, double mean, double b, double ampl_re, double ampl_im,
+                            double offset_re, double offset_im, void *table);
+PCX_API int pcx_noise_next_offset(pcx_noise *h, size_t *draw);
+
+/* ===================================================================== *
  *  /comms/rotate, /comms/scale, /comms/abs, /comms/conjugate   (math/)
  *  Stateless maps; n counts stream elements times dtype.dimension().
  * ===================================================================== */

@@ -63,6 +63,9 @@ PCXB_API int pcxb_get_sizes(pcxb_block *b, const char *name, size_t *out, size_t
  * bytes go to out.  An unsigned argument (setThreshold) travels through pcxb_call_size / pcxb_get_size. */
 PCXB_API int pcxb_call_bytes(pcxb_block *b, const char *name, const unsigned char *v, size_t n);
 PCXB_API int pcxb_get_bytes(pcxb_block *b, const char *name, unsigned char *out, size_t cap, size_t *n);
+/* one std::complex<double> (setOffset / setAmplitude of /comms/waveform_source and /comms/noise_source, and their getters) */
+PCXB_API int pcxb_call_complex(pcxb_block *b, const char *name, double re, double im);
+PCXB_API int pcxb_get_complex(pcxb_block *b, const char *name, double *re, double *im);
 PCXB_API int pcxb_get_double(pcxb_block *b, const char *name, double *out);
 PCXB_API int pcxb_get_size(pcxb_block *b, const char *name, size_t *out);
 PCXB_API int pcxb_get_int64(pcxb_block *b, const char *name, int64_t *out);
@@ -131,7 +134,8 @@ PCXB_API int pcxb_num_ports(pcxb_block *b, int is_output, size_t *count);
 PCXB_API int pcxb_port_info(pcxb_block *b, int is_output, size_t i, char *name, size_t name_cap, char *dtype, size_t dtype_cap,
                             size_t *dimension, size_t *bytes, size_t *preloaded);
 /* one work() call on planted buffers for every port: workInfo().minElements = minimum over the
- * indexed ports, minAllElements over all of them; no labels on this path */
+ * indexed ports, minAllElements over all of them; no labels on this path.  A block without inputs (the two sources of the
+ * waveform module) is driven through here with nin = 0: ins, in_elems and consumed may then be NULL. */
 PCXB_API int pcxb_work_ports(pcxb_block *b, size_t nin, const void *const *ins, const size_t *in_elems, size_t nout,
                              void *const *outs, const size_t *out_elems, size_t *consumed, size_t *produced);
 

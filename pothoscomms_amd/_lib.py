@@ -23,6 +23,9 @@ SCR_SCAN, SCR_SERIAL = 0, 1          # pcx_scrambler_get_plan
 PRE_PLANES, PRE_BYTES = 0, 1         # pcx_preamble_get_plan
 DIFF_SCAN, DIFF_SERIAL = 0, 1        # pcx_diffcode_get_plan
 REPACK_BITS_TO_SYMBOLS, REPACK_SYMBOLS_TO_BITS, REPACK_BYTES_TO_SYMBOLS, REPACK_SYMBOLS_TO_BYTES = 0, 1, 2, 3      # pcx_repack_create
+WAVE_CONST, WAVE_SINE, WAVE_RAMP, WAVE_SQUARE = 0, 1, 2, 3                       # pcx_waveform_table
+NOISE_UNIFORM, NOISE_NORMAL, NOISE_LAPLACE, NOISE_POISSON = 0, 1, 2, 3           # pcx_noise_table
+NOISE_ENTRIES = 4096
 
 
 class PcxError(RuntimeError):
@@ -200,6 +203,19 @@ SIGNATURES = {
     "pcx_repack_get_geometry": (_i, [_vp, _psz, _psz]),
     "pcx_repack_process": (_i, [_vp, _vp, _vp, _sz]),
     "pcx_repack_process_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_source_create": (_i, [_i, _i, C.POINTER(_vp)]),
+    "pcx_source_destroy": (_i, [_vp]),
+    "pcx_source_set_table": (_i, [_vp, _vp, _sz, C.c_uint64]),
+    "pcx_source_get_index": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "pcx_source_set_index": (_i, [_vp, C.c_uint64]),
+    "pcx_source_get_geometry": (_i, [_vp, _psz, _psz, C.POINTER(_i)]),
+    "pcx_source_generate": (_i, [_vp, _vp, _sz]),
+    "pcx_source_generate_dev": (_i, [_vp, _vp, _sz, _vp]),
+    "pcx_waveform_table": (_i, [_i, _i, _i, _d, _d, _d, _d, _d, _d, _d, _vp, _sz, _psz, C.POINTER(C.c_uint64)]),
+    "pcx_noise_create": (_i, [_i, C.c_uint32, C.POINTER(_vp)]),
+    "pcx_noise_destroy": (_i, [_vp]),
+    "pcx_noise_table": (_i, [_vp, _i, _i, _i, _d, _d, _d, _d, _d, _d, _vp]),
+    "pcx_noise_next_offset": (_i, [_vp, _psz]),
     "pcx_rotate": (_i, [_i, _d, _d, _vp, _vp, _sz]),
     "pcx_rotate_dev": (_i, [_i, _d, _d, _vp, _vp, _sz, _vp]),
     "pcx_scale": (_i, [_i, _i, _d, _vp, _vp, _sz]),

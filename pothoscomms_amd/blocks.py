@@ -33,11 +33,13 @@ _blib = None
 # /comms/descrambler), "correlator" libpcx_correlator_blocks.so (correlator_blocks.cpp: /comms/preamble_correlator), "symbol"
 # libpcx_symbol_blocks.so (symbol_blocks.cpp: /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder,
 # /comms/differential_decoder), "repack" libpcx_repack_blocks.so (repack_blocks.cpp: /comms/bits_to_symbols, /comms/symbols_to_bits,
-# /comms/bytes_to_symbols, /comms/symbols_to_bytes) -- one registry each, as Pothos loads one module library per source directory
+# /comms/bytes_to_symbols, /comms/symbols_to_bytes), "waveform" libpcx_waveform_blocks.so (waveform_blocks.cpp: /comms/waveform_source,
+# /comms/noise_source) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
-           "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so")}
+           "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so"),
+           "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so")}
 _mlibs = {}
 
 
@@ -80,6 +82,8 @@ def load(module="comms"):
     L.pcxb_call_string.argtypes = [vp, cp, cp]
     L.pcxb_call_taps.argtypes = [vp, cp, vp, sz, i]
     L.pcxb_get_double.argtypes = [vp, cp, C.POINTER(C.c_double)]
+    L.pcxb_call_complex.argtypes = [vp, cp, C.c_double, C.c_double]
+    L.pcxb_get_complex.argtypes = [vp, cp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.pcxb_get_size.argtypes = [vp, cp, C.POINTER(sz)]
     L.pcxb_get_bool.argtypes = [vp, cp, C.POINTER(i)]
     L.pcxb_get_string.argtypes = [vp, cp, cp, sz]
@@ -194,6 +198,12 @@ class Block:
             self.in_dtype = self.out_dtype = None
             self.in_dim = self.out_dim = 0
             return
+        nin = C.c_size_t()
+        _check_in(self._module, L.pcxb_num_ports(self._h, 0, C.byref(nin)))
+        if nin.value == 0:                    # a source: driven through work_ports with no inputs
+            self.in_dtype, self.in_dim = None, 0
+            self.out_dtype, self.out_dim, _ = self._port(1)
+            return
         self.in_dtype, self.in_dim, _ = self._port(0)
         self.out_dtype, self.out_dim, _ = self._port(1)
 
@@ -249,6 +259,13 @@ class Block:
             v = C.c_int64()
             _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
             return v.value
+        if name in ("setOffset", "setAmplitude"):       # std::complex<double>
+            v = complex(args[0])
+            return _check_in(self._module, L.pcxb_call_complex(self._h, n, v.real, v.imag))
+        if name in ("getOffset", "getAmplitude"):
+            re, im = C.c_double(), C.c_double()
+            _check_in(self._module, L.pcxb_get_complex(self._h, n, C.byref(re), C.byref(im)))
+            return complex(re.value, im.value)
         if name == "setPreamble":               # std::vector<unsigned char>
             v = np.ascontiguousarray(np.asarray(args[0], dtype=np.uint8).reshape(-1))
             return _check_in(self._module, L.pcxb_call_bytes(self._h, n, v.ctypes.data_as(C.c_void_p) if v.size else None, v.size))
@@ -267,7 +284,7 @@ class Block:
                 _check_in(self._module, L.pcxb_get_bool(self._h, n, C.byref(v)))
                 return bool(v.value)
             if name in ("getPhase", "getFactor", "sampleRate", "frequencyLower", "frequencyUpper", "bandwidthTrans", "alpha",
-                        "stopDB", "passDB", "gain", "getAttack", "getRelease"):
+                        "stopDB", "passDB", "gain", "getAttack", "getRelease", "getFrequency", "getSampleRate", "getResolution", "getMean", "getB"):
                 v = C.c_double()
                 _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
                 return v.value
@@ -386,6 +403,15 @@ class Block:
         _check_in(self._module, L.pcxb_work_ports(self._h, len(xs), in_ptrs, in_n, len(ys), out_ptrs, out_n, cons, prod))
         produced = [int(v) for v in prod]
         return [y[:p * port[2]] for y, p, port in zip(ys, produced, op)], [int(v) for v in cons], produced
+
+    def work_ports_raw(self, in_ptrs, in_elems, out_ptrs, out_elems):
+        """pcxb_work_ports on raw buffer addresses (host or device memory), one per port; a block without inputs takes two empty lists.
+        Returns (consumed, produced), one entry per port."""
+        ins, outs = (C.c_void_p * len(in_ptrs))(*in_ptrs), (C.c_void_p * len(out_ptrs))(*out_ptrs)
+        nin, nout = (C.c_size_t * len(in_ptrs))(*in_elems), (C.c_size_t * len(out_ptrs))(*out_elems)
+        cons, prod = (C.c_size_t * len(in_ptrs))(), (C.c_size_t * len(out_ptrs))()
+        _check_in(self._module, load(self._module).pcxb_work_ports(self._h, len(in_ptrs), ins, nin, len(out_ptrs), outs, nout, cons, prod))
+        return [int(v) for v in cons], [int(v) for v in prod]
 
     def work(self, inbuf, out_elems, labels=(), outbuf=None, label_cap=64):
         """One work() call.  Returns (out[:produced], consumed, produced, reserve, posted_labels).

@@ -124,6 +124,7 @@ public:
     Object(const char *s) : _t(&typeid(std::string)), _s(s) {}
     Object(const std::string &s) : _t(&typeid(std::string)), _s(s) {}
     Object(const DType &d) : _t(&typeid(DType)), _i((long long)d.dimension()), _s(d.name()) {}
+    Object(const std::complex<double> &v) : _t(&typeid(std::complex<double>)), _d(v.real()), _im(v.imag()) {}     // waveform/WaveformSource.cpp:121
     Object(const std::vector<double> &v) : _t(&typeid(std::vector<double>)), _vd(v) {}
     Object(const std::vector<std::complex<double>> &v) : _t(&typeid(std::vector<std::complex<double>>)), _vc(v) {}
     Object(const std::vector<size_t> &v) : _t(&typeid(std::vector<size_t>)), _vs(v) {}
@@ -145,6 +146,7 @@ public:
                               to == typeid(float) || to == typeid(double);
         if (toNumber) return isNumber();
         if (to == typeid(DType)) return *_t == typeid(std::string);
+        if (to == typeid(std::complex<double>)) return isNumber();
         if (to == typeid(std::vector<std::complex<double>>)) return *_t == typeid(std::vector<double>);
         if (to == typeid(std::vector<size_t>)) return *_t == typeid(std::vector<double>);
         return false;
@@ -166,6 +168,11 @@ private:
         return (T)_i;
     }
     std::string get(std::string *) const { return _s; }
+    std::complex<double> get(std::complex<double> *) const
+    {
+        if (*_t == typeid(std::complex<double>)) return std::complex<double>(_d, _im);
+        return std::complex<double>(get(static_cast<double *>(nullptr)), 0.0);
+    }
     DType get(DType *) const { return *_t == typeid(DType) ? DType(_s, (size_t)_i) : DType(_s); }
     std::vector<double> get(std::vector<double> *) const { return _vd; }
     std::vector<std::complex<double>> get(std::vector<std::complex<double>> *) const
@@ -180,7 +187,7 @@ private:
     }
     std::vector<unsigned char> get(std::vector<unsigned char> *) const { return _vb; }
     const std::type_info *_t;
-    double _d = 0;
+    double _d = 0, _im = 0;
     long long _i = 0;
     std::string _s;
     std::vector<double> _vd;

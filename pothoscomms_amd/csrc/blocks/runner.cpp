@@ -169,6 +169,18 @@ int pcxb_get_bytes(pcxb_block *b, const char *name, unsigned char *out, size_t c
         for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
     });
 }
+int pcxb_call_complex(pcxb_block *b, const char *name, double re, double im)
+{
+    return guarded([&] { b->blk->call(name, {Object(std::complex<double>(re, im))}); });
+}
+int pcxb_get_complex(pcxb_block *b, const char *name, double *re, double *im)
+{
+    return guarded([&] {
+        const auto v = b->blk->call(name).convert<std::complex<double>>();
+        *re = v.real();
+        *im = v.imag();
+    });
+}
 int pcxb_get_double(pcxb_block *b, const char *name, double *out) { return guarded([&] { *out = b->blk->call(name).convert<double>(); }); }
 int pcxb_get_size(pcxb_block *b, const char *name, size_t *out) { return guarded([&] { *out = b->blk->call(name).convert<unsigned long>(); }); }
 int pcxb_get_int64(pcxb_block *b, const char *name, int64_t *out) { return guarded([&] { *out = (int64_t)b->blk->call(name).convert<long long>(); }); }

@@ -325,6 +325,18 @@ size_t repack_slice(int kind, unsigned w);
 size_t repack_out_elems(int kind, unsigned w, size_t in_elems);     // of a whole number of groups
 // one slice of m input elements, a whole number of groups
 int launch_repack_slice(int kind, unsigned w, bool msb, const void *in, void *out, size_t m, hipStream_t st);
+// (source.hip) /comms/waveform_source, /comms/noise_source: one period of the table walk and the wrapped copy of it
+size_t source_tile_bytes();                                         // output bytes per workgroup and pass
+size_t source_lds_bytes();                                          // the longest period a workgroup stages in LDS
+size_t source_max_entries();
+size_t source_seq_bytes(size_t period, size_t es);                  // bytes of the period as it is written out
+// seq[j] = table[(index + j * step) & (entries - 1)] for the period and what source_seq_bytes adds to it
+int launch_source_permute(size_t es, const void *table, void *seq, uint64_t index, uint64_t step, size_t entries, size_t period, hipStream_t st);
+// nbytes of output from byte `phase` of the period on; period_bytes: a power of two of at least 16
+int launch_source_copy(const void *seq, void *out, size_t nbytes, size_t phase, size_t period_bytes, hipStream_t st);
+// the per-element gather of the diagnostic build, and whether PCX_SRC_GATHER selects it there
+bool source_gather_selected();
+int launch_source_gather(size_t es, const void *table, void *out, uint64_t index, uint64_t step, size_t entries, size_t n, hipStream_t st);
 // out[i] = angle(in[i]*_prev); _prev(i=0) := *prev_in (already conjugated); *prev_out := conj(in[n-1])
 int launch_freqdemod(int scalar, const void *in, void *out, size_t n, const void *prev_in, void *prev_out, hipStream_t st);
 int launch_fill_uniform_f32(float *dst, size_t n, uint64_t seed, uint64_t offset, hipStream_t st);

@@ -833,6 +833,145 @@ class SymbolRepacker(_Handle):
         return out
 
 
+WAVES = {"CONST": _lib.WAVE_CONST, "SINE": _lib.WAVE_SINE, "RAMP": _lib.WAVE_RAMP, "SQUARE": _lib.WAVE_SQUARE}
+NOISE_WAVES = {"UNIFORM": _lib.NOISE_UNIFORM, "NORMAL": _lib.NOISE_NORMAL, "LAPLACE": _lib.NOISE_LAPLACE, "POISSON": _lib.NOISE_POISSON}
+
+
+def waveform_table(dtype, wave, rate=1.0, freq=0.0, res=0.0, ampl=1.0, offset=0.0):
+    """pcx_waveform_table: (table, step) of the waveform source at these settings, built on the host as WaveformSource.cpp:178-259
+    builds it.  ampl and offset are complex.  The table is (entries, 2) for a complex type, (entries,) for a real one."""
+    scalar, cplx = parse_dtype(dtype)
+    if wave not in WAVES:
+        raise _lib.InvalidArgument(_lib.ERR_ARG, "unknown waveform setting")
+    ampl, offset = complex(ampl), complex(offset)
+    args = (scalar, int(cplx), WAVES[wave], float(rate), float(freq), float(res), ampl.real, ampl.imag, offset.real, offset.imag)
+    entries, step = C.c_size_t(), C.c_uint64()
+    _lib.check(_lib.load().pcx_waveform_table(*args, None, 0, C.byref(entries), C.byref(step)))
+    table = np.zeros((entries.value, 2) if cplx else (entries.value,), NP_SCALAR[scalar])
+    _lib.check(_lib.load().pcx_waveform_table(*args, _np_ptr(table), entries.value, C.byref(entries), C.byref(step)))
+    return table, step.value
+
+
+class NoiseGenerator(_Handle):
+    """pcx_noise_*: the std::mt19937 of the noise source and its four distributions as NoiseSource.cpp:188-250 calls them (host only).
+    seed None: from std::random_device, as the reference's constructor does."""
+    _destroy = "pcx_noise_destroy"
+
+    def __init__(self, seed=None):
+        super().__init__()
+        _lib.check(_lib.load().pcx_noise_create(int(seed is not None), int(seed or 0) & 0xFFFFFFFF, C.byref(self._h)))
+
+    def table(self, dtype, wave, mean=0.0, b=1.0, ampl=1.0, offset=0.0):
+        """the next 4096-entry table of the generator (every call draws on)"""
+        scalar, cplx = parse_dtype(dtype)
+        if wave not in NOISE_WAVES:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "unknown waveform setting")
+        ampl, offset = complex(ampl), complex(offset)
+        table = np.zeros((_lib.NOISE_ENTRIES, 2) if cplx else (_lib.NOISE_ENTRIES,), NP_SCALAR[scalar])
+        _lib.check(_lib.load().pcx_noise_table(self._h, scalar, int(cplx), NOISE_WAVES[wave], float(mean), float(b), ampl.real, ampl.imag,
+                                               offset.real, offset.imag, _np_ptr(table)))
+        return table
+
+    def next_offset(self):
+        """the draw in front of every work(): uniform over 0 ... 4095"""
+        v = C.c_size_t()
+        _lib.check(_lib.load().pcx_noise_next_offset(self._h, C.byref(v)))
+        return v.value
+
+
+class TableSource(_Handle):
+    """pcx_source_*: the cyclic walk of a table of the stream type from a carried 64-bit index, out[i] = table[(index + i * step) &
+    (entries - 1)].  The index is host state and advances when a call is made."""
+    _destroy = "pcx_source_destroy"
+
+    def __init__(self, dtype):
+        super().__init__()
+        self.scalar, self.cplx = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_source_create(self.scalar, int(self.cplx), C.byref(self._h)))
+
+    def set_table(self, table, step, entries=None):
+        """table: (entries, 2) resp. (entries,) of the stream type, or any contiguous array of that many bytes with `entries` given"""
+        t = as_pairs(table)
+        _lib.check(_lib.load().pcx_source_set_table(self._h, _np_ptr(t), t.shape[0] if entries is None else int(entries), int(step) & ((1 << 64) - 1)))
+
+    def index(self):
+        v = C.c_uint64()
+        _lib.check(_lib.load().pcx_source_get_index(self._h, C.byref(v)))
+        return v.value
+
+    def set_index(self, index):
+        _lib.check(_lib.load().pcx_source_set_index(self._h, int(index) & ((1 << 64) - 1)))
+
+    def geometry(self):
+        """(tile, period, staged): elements per workgroup pass, elements after which the stream repeats, whether the period sits in LDS"""
+        t, p, s = C.c_size_t(), C.c_size_t(), C.c_int()
+        _lib.check(_lib.load().pcx_source_get_geometry(self._h, C.byref(t), C.byref(p), C.byref(s)))
+        return t.value, p.value, bool(s.value)
+
+    def generate(self, n, out=None, stream=None):
+        """the next n elements: into a fresh numpy array, into `out` (numpy: on return; a CUDA/ROCm tensor or a raw device address:
+        enqueued on `stream`)"""
+        n = int(n)
+        if out is None:
+            out = np.zeros((n, 2) if self.cplx else (n,), NP_SCALAR[self.scalar])
+        if isinstance(out, np.ndarray):
+            if not out.flags.c_contiguous or out.dtype != NP_SCALAR[self.scalar] or out.size < n * (2 if self.cplx else 1):
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "source: %s%s output for %d elements" % (out.dtype, out.shape, n))
+            _lib.check(_lib.load().pcx_source_generate(self._h, _np_ptr(out), n))
+            return out
+        ptr = C.c_void_p(out) if isinstance(out, int) else _dev_ptr(out)
+        _lib.check(_lib.load().pcx_source_generate_dev(self._h, ptr, n, _stream_ptr(stream)))
+        return out
+
+
+class WaveformSource(TableSource):
+    """/comms/waveform_source without the block around it: the settings of WaveformSource.cpp, the table built on the host from them
+    at once (there is no activation here) and walked on the device.  The index survives every setter."""
+
+    def __init__(self, dtype="complex_float32", wave="CONST", rate=1.0, freq=0.0, res=0.0, ampl=1.0, offset=0.0):
+        super().__init__(dtype)
+        self._dtype = (self.scalar, self.cplx)
+        self.settings = dict(wave=wave, rate=rate, freq=freq, res=res, ampl=ampl, offset=offset)
+        self.update()
+
+    def update(self, **settings):
+        """change any of wave, rate, freq, res, ampl, offset and rebuild the table"""
+        unknown = set(settings) - set(self.settings)
+        if unknown:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "waveform source: unknown setting %s" % ", ".join(sorted(unknown)))
+        self.settings.update(settings)
+        self.table, self.step = waveform_table(self._dtype, **self.settings)
+        self.set_table(self.table, self.step)
+
+
+class NoiseSource(TableSource):
+    """/comms/noise_source without the block around it: a NoiseGenerator, its table at the settings, and the draw that moves the
+    index in front of every generate()."""
+
+    def __init__(self, dtype="complex_float32", wave="NORMAL", mean=0.0, b=1.0, ampl=1.0, offset=0.0, seed=None):
+        super().__init__(dtype)
+        self._dtype = (self.scalar, self.cplx)
+        self.gen = NoiseGenerator(seed)
+        self.settings = dict(wave=wave, mean=mean, b=b, ampl=ampl, offset=offset)
+        self.update()
+
+    def update(self, **settings):
+        unknown = set(settings) - set(self.settings)
+        if unknown:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "noise source: unknown setting %s" % ", ".join(sorted(unknown)))
+        self.settings.update(settings)
+        self.table = self.gen.table(self._dtype, **self.settings)
+        self.set_table(self.table, 1)
+
+    def generate(self, n, out=None, stream=None):
+        self.set_index(self.index() + self.gen.next_offset())
+        return super().generate(n, out, stream)
+
+    def close(self):
+        self.gen.close()
+        super().close()
+
+
 class FmChain(_Handle):
     """pcx_fmchain_*: Rotate -> FIR -> FreqDemod in one kernel (complex_float32 -> float32)."""
     _destroy = "pcx_fmchain_destroy"
