@@ -465,6 +465,45 @@ PCX_API int pcx_preamble_distances(pcx_preamble *h, const void *in, size_t n_in,
 PCX_API int pcx_preamble_distances_dev(pcx_preamble *h, const void *in_dev, size_t n_in, uint32_t *dist_dev, void *stream);
 
 /* ===================================================================== *
+ *  /comms/threshold      utility/Threshold.cpp
+ *
+ *  A real stream against two levels, one bit of carried state (:130-144): an inactive block turns active at an element
+ *  x > activation, otherwise an active one turns inactive at x < deactivation.  Every label of the reference marks such a change,
+ *  so the two kinds alternate: a call returns ONE ascending list of transition indices and the state in which it was entered, and
+ *  transition j is an activation exactly when (entry state + j) is even.  The comparisons are the element type's own (a NaN
+ *  element or level compares false, int64 never passes through double): every index equals the reference's.
+ * ===================================================================== */
+typedef struct pcx_threshold pcx_threshold;
+/* ThresholdFactory (:163-174): scalar in {F64, F32, I64, I32, I16, I8}, anything else is PCX_ERR_ARG.  Both levels 0, inactive
+ * (:54-58).  Where a device can be reached the workspace of one slice is allocated here; otherwise at the first call that computes. */
+PCX_API int pcx_threshold_create(pcx_threshold **out, int scalar);
+PCX_API int pcx_threshold_destroy(pcx_threshold *h);
+/* each pointer addresses ONE ELEMENT of the handle's type (an int64 level keeps its 64 bits) */
+PCX_API int pcx_threshold_set_levels(pcx_threshold *h, const void *activation, const void *deactivation);
+PCX_API int pcx_threshold_get_levels(const pcx_threshold *h, void *activation, void *deactivation);
+/* activate() (:111-115): inactive again.  get_state / set_state read and write the carried state (0 inactive, else active).
+ * All three wait for what the handle has in flight. */
+PCX_API int pcx_threshold_reset(pcx_threshold *h);
+PCX_API int pcx_threshold_get_state(pcx_threshold *h, int *active);
+PCX_API int pcx_threshold_set_state(pcx_threshold *h, int active);
+/* elements a workgroup and a call slice hold (the seams a test wants to straddle) */
+PCX_API int pcx_threshold_get_geometry(size_t *tile, size_t *slice);
+/* work() (:117-149) on in[0 .. n): idx receives the indices of the elements at which the state changed, ascending, the first
+ * min(*n_transitions, idx_cap) of them; *n_transitions is always the full count, *state_in the state the call was entered in; the
+ * carried state advances whatever idx_cap is.  out, when not NULL, receives the n elements (out == in is allowed, any other overlap
+ * is PCX_ERR_ARG).  n == 0 stores nothing, leaves the state alone and reports (0, the state).  Checked in this order before any
+ * device call: the handle, the counts, in, idx_cap without idx, the overlap.  process_dev takes device pointers throughout;
+ * counts_dev receives three words: n, the transitions, the entry state.  It allocates nothing and synchronises nothing: it can be
+ * captured into a graph. */
+PCX_API int pcx_threshold_process(pcx_threshold *h, const void *in, size_t n, void *out, uint64_t *idx, size_t idx_cap, size_t *n_transitions,
+                                  int *state_in);
+PCX_API int pcx_threshold_process_dev(pcx_threshold *h, const void *in_dev, size_t n, void *out_dev, uint64_t *idx_dev, size_t idx_cap,
+                                      uint64_t *counts_dev, void *stream);
+/* the state AFTER every element, one byte each (0 / 1), entered in the carried state -- which these two calls leave as it is */
+PCX_API int pcx_threshold_states(pcx_threshold *h, const void *in, size_t n, unsigned char *states);
+PCX_API int pcx_threshold_states_dev(pcx_threshold *h, const void *in_dev, size_t n, unsigned char *states_dev, void *stream);
+
+/* ===================================================================== *
  *  /comms/symbol_mapper      digital/SymbolMapper.cpp
  *
  *  out[i] = map[in[i] & mask] (:89-91): one unsigned char in, one element of the stream type out.  Exact.

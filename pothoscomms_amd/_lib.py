@@ -170,6 +170,18 @@ SIGNATURES = {
     "pcx_preamble_process_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "pcx_preamble_distances": (_i, [_vp, _vp, _sz, _vp, _psz]),
     "pcx_preamble_distances_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "pcx_threshold_create": (_i, [C.POINTER(_vp), _i]),
+    "pcx_threshold_destroy": (_i, [_vp]),
+    "pcx_threshold_set_levels": (_i, [_vp, _vp, _vp]),
+    "pcx_threshold_get_levels": (_i, [_vp, _vp, _vp]),
+    "pcx_threshold_reset": (_i, [_vp]),
+    "pcx_threshold_get_state": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_threshold_set_state": (_i, [_vp, _i]),
+    "pcx_threshold_get_geometry": (_i, [_psz, _psz]),
+    "pcx_threshold_process": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _psz, C.POINTER(_i)]),
+    "pcx_threshold_process_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "pcx_threshold_states": (_i, [_vp, _vp, _sz, _vp]),
+    "pcx_threshold_states_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "pcx_mapper_create": (_i, [_i, _i, C.POINTER(_vp)]),
     "pcx_mapper_destroy": (_i, [_vp]),
     "pcx_mapper_set_map": (_i, [_vp, _vp, _sz]),

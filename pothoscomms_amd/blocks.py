@@ -34,12 +34,13 @@ _blib = None
 # libpcx_symbol_blocks.so (symbol_blocks.cpp: /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder,
 # /comms/differential_decoder), "repack" libpcx_repack_blocks.so (repack_blocks.cpp: /comms/bits_to_symbols, /comms/symbols_to_bits,
 # /comms/bytes_to_symbols, /comms/symbols_to_bytes), "waveform" libpcx_waveform_blocks.so (waveform_blocks.cpp: /comms/waveform_source,
-# /comms/noise_source) -- one registry each, as Pothos loads one module library per source directory
+# /comms/noise_source), "utility" libpcx_utility_blocks.so (utility_blocks.cpp: /comms/threshold) -- one registry each, as Pothos loads
+# one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
            "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so"),
-           "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so")}
+           "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so")}
 _mlibs = {}
 
 
@@ -266,6 +267,18 @@ class Block:
             re, im = C.c_double(), C.c_double()
             _check_in(self._module, L.pcxb_get_complex(self._h, n, C.byref(re), C.byref(im)))
             return complex(re.value, im.value)
+        if name in ("setActivationLevel", "setDeactivationLevel"):      # one element of the stream type: an integer level keeps its 64 bits
+            if str(self.dtype).startswith("float"):
+                return _check_in(self._module, L.pcxb_call_double(self._h, n, float(args[0])))
+            return _check_in(self._module, L.pcxb_call_int64(self._h, n, int(args[0])))
+        if name in ("getActivationLevel", "getDeactivationLevel"):
+            if str(self.dtype).startswith("float"):
+                v = C.c_double()
+                _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
+            else:
+                v = C.c_int64()
+                _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
+            return v.value
         if name == "setPreamble":               # std::vector<unsigned char>
             v = np.ascontiguousarray(np.asarray(args[0], dtype=np.uint8).reshape(-1))
             return _check_in(self._module, L.pcxb_call_bytes(self._h, n, v.ctypes.data_as(C.c_void_p) if v.size else None, v.size))

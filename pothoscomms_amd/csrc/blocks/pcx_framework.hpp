@@ -143,7 +143,8 @@ public:
         const Object probe(0.0);
         const bool toNumber = to == typeid(bool) || to == typeid(int) || to == typeid(long) || to == typeid(long long) ||
                               to == typeid(unsigned) || to == typeid(unsigned long) || to == typeid(unsigned long long) ||
-                              to == typeid(float) || to == typeid(double);
+                              to == typeid(float) || to == typeid(double) ||
+                              to == typeid(short) || to == typeid(signed char);      // utility/Threshold.cpp:71, int16_t and int8_t levels
         if (toNumber) return isNumber();
         if (to == typeid(DType)) return *_t == typeid(std::string);
         if (to == typeid(std::complex<double>)) return isNumber();

@@ -302,6 +302,29 @@ int launch_pre_slice(const PreShape &p, const void *in, void *out, size_t m, con
                      int first, uint64_t npos, uint64_t *npos_out, uint64_t *nmatch_out, uint64_t *idx, uint64_t cap, hipStream_t st);
 int launch_pre_empty(uint64_t *state, uint64_t *npos_out, uint64_t *nmatch_out, hipStream_t st);
 int launch_pre_distances(const PreShape &p, const void *in, size_t m, const uint32_t *pw, const unsigned char *pre, uint32_t *dist, hipStream_t st);
+// (threshold.hip) /comms/threshold: the levels of a configured handle and one call slice
+struct ThrShape {
+    int scalar = PCX_F64;
+    unsigned char act[8] = {}, deact[8] = {};   // one element of the stream type each
+};
+struct ThrWork {                            // workspace of one slice: the two mask rows of every tile, a record and an offset per tile;
+    uint64_t *mask = nullptr;
+    uint32_t *rec = nullptr, *toff = nullptr;
+    uint64_t *tot = nullptr;                // [0] transitions of the call so far, [1] those in front of the slice, [2] the call's entry state
+    uint64_t *carry = nullptr;              // the state carried from call to call
+    uint64_t *walk = nullptr;               // the state a pcx_threshold_states call carries from slice to slice
+};
+size_t thr_tile();                          // elements per workgroup, per slice
+size_t thr_slice();
+size_t thr_mask_words();                    // 64-bit words a tile leaves: its row of x > activation, then that of x < deactivation
+// one slice of m elements from in[0], pos0 elements into the call: the first min(transitions, cap) stream indices go to idx behind those
+// of the earlier slices, out (or null) receives the m elements, the carried state advances; first: the call's first slice; the last
+// slice passes the three device words that receive (elements, transitions, entry state) of the call (else null)
+int launch_thr_slice(const ThrShape &p, const void *in, void *out, size_t m, const ThrWork &w, uint64_t pos0, int first, uint64_t nelem,
+                     uint64_t *counts_out, uint64_t *idx, uint64_t cap, hipStream_t st);
+int launch_thr_empty(const ThrWork &w, uint64_t *counts_out, hipStream_t st);
+// the state after each of the m elements, one byte each; the carried state is the entry state of the first slice and stays as it is
+int launch_thr_states(const ThrShape &p, const void *in, size_t m, const ThrWork &w, int first, unsigned char *states, hipStream_t st);
 // (symbols.hip) /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder, /comms/differential_decoder
 struct DiffShape {
     int decode = 0;

@@ -608,6 +608,88 @@ class PreambleCorrelator(_Handle):
         _lib.check(_lib.load().pcx_preamble_distances_dev(self._h, _dev_ptr(x), n_in, _dev_ptr(dist), _stream_ptr(stream)))
 
 
+class Threshold(_Handle):
+    """pcx_threshold_*: utility/Threshold.cpp's comparison of a real stream against an activation and a deactivation level with one
+    bit of carried state.  A call returns the ascending indices of the elements at which the state changed and the
+    state it was entered in: transition j is an activation exactly when (state_in + j) is even.  Levels are converted to the
+    element type by numpy."""
+    _destroy = "pcx_threshold_destroy"
+
+    def __init__(self, dtype="float64", activation=0, deactivation=0):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, cplx = parse_dtype(dtype)
+        if cplx:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "threshold: %s is not a real type" % (dtype,))
+        _lib.check(_lib.load().pcx_threshold_create(C.byref(self._h), self.scalar))
+        self.np_dtype = np.dtype(NP_SCALAR[self.scalar])
+        if activation != 0 or deactivation != 0:
+            self.set_levels(activation, deactivation)
+
+    def set_levels(self, activation, deactivation):
+        lv = np.array([activation, deactivation], dtype=self.np_dtype)
+        _lib.check(_lib.load().pcx_threshold_set_levels(self._h, _np_ptr(lv[0:1]), _np_ptr(lv[1:2])))
+
+    def levels(self):
+        lv = np.zeros(2, self.np_dtype)
+        _lib.check(_lib.load().pcx_threshold_get_levels(self._h, _np_ptr(lv[0:1]), _np_ptr(lv[1:2])))
+        return lv[0], lv[1]
+
+    def reset(self):
+        _lib.check(_lib.load().pcx_threshold_reset(self._h))
+
+    def state(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_threshold_get_state(self._h, C.byref(v)))
+        return v.value
+
+    def set_state(self, active):
+        _lib.check(_lib.load().pcx_threshold_set_state(self._h, int(bool(active))))
+
+    @staticmethod
+    def geometry():
+        """(tile, slice): the elements a workgroup and a call slice hold"""
+        v = [C.c_size_t() for _ in range(2)]
+        _lib.check(_lib.load().pcx_threshold_get_geometry(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _elements(self, x):
+        x = np.ascontiguousarray(x)
+        if x.dtype != self.np_dtype or x.ndim != 1:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "threshold: %s%s input for a %s block" % (x.dtype, x.shape, self.dtype))
+        return x
+
+    def process(self, x, cap=None, out=None):
+        """x: (n,) of the element type -> (transition indices as uint64, n_transitions, state_in).  At most `cap` indices come back
+        (default: every element could be a transition); n_transitions is the full count.  out: an array of the element type that
+        receives the n forwarded elements (x itself: in place)."""
+        x = self._elements(x)
+        cap = x.shape[0] if cap is None else int(cap)
+        idx = np.zeros(max(cap, 1), np.uint64)
+        nt, entry = C.c_size_t(), C.c_int()
+        if out is not None and not (isinstance(out, np.ndarray) and out.dtype == self.np_dtype and out.flags.c_contiguous and out.size >= x.shape[0]):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "threshold: out must be a contiguous %s array of n elements" % self.np_dtype)
+        _lib.check(_lib.load().pcx_threshold_process(self._h, _np_ptr(x), x.shape[0], None if out is None else _np_ptr(out), _np_ptr(idx), cap,
+                                                     C.byref(nt), C.byref(entry)))
+        return idx[:min(nt.value, cap)].copy(), nt.value, entry.value
+
+    def states(self, x):
+        """x: (n,) of the element type -> the state after every element as uint8; the carried state is read and left as it is"""
+        x = self._elements(x)
+        s = np.zeros(max(1, x.shape[0]), np.uint8)
+        _lib.check(_lib.load().pcx_threshold_states(self._h, _np_ptr(x), x.shape[0], _np_ptr(s)))
+        return s[:x.shape[0]]
+
+    def process_dev(self, x, n, idx, cap, counts, out=None, stream=None):
+        """device tensors: x of the element type, idx int64 / uint64 of at least cap elements, counts three 64-bit words that receive
+        (n, n_transitions, state_in), out of the element type (x itself: in place) or None; nothing is allocated or synchronised"""
+        _lib.check(_lib.load().pcx_threshold_process_dev(self._h, _dev_ptr(x), n, None if out is None else _dev_ptr(out),
+                                                         _dev_ptr(idx) if cap else None, cap, _dev_ptr(counts), _stream_ptr(stream)))
+
+    def states_dev(self, x, n, states, stream=None):
+        _lib.check(_lib.load().pcx_threshold_states_dev(self._h, _dev_ptr(x), n, _dev_ptr(states), _stream_ptr(stream)))
+
+
 class _SymbolMap(_Handle):
     """what pcx_mapper_* and pcx_slicer_* share: a map in the stream type's own element layout"""
     _family = None
