@@ -504,6 +504,81 @@ PCX_API int pcx_threshold_states(pcx_threshold *h, const void *in, size_t n, uns
 PCX_API int pcx_threshold_states_dev(pcx_threshold *h, const void *in_dev, size_t n, unsigned char *states_dev, void *stream);
 
 /* ===================================================================== *
+ *  /comms/preamble_framer      digital/PreambleFramer.cpp
+ *  /comms/frame_insert         digital/FrameInsert.cpp, digital/FrameHelper.hpp
+ *
+ *  A stream with a preamble in front of every start label and zero padding behind every end label.  The framer works on bytes; the
+ *  inserter on complex symbols, where every preamble symbol is repeated symbol_width times and 58 BPSK header symbols follow: the
+ *  Hamming(8,4)-coded id, twelve bits of the length and a checksum over id and all sixteen bits of the length.  The host walks the
+ *  call's labels as the reference's loop does and one kernel writes the framed stream as ONE buffer.  Every output
+ *  element is a copy, a zero or a sign flip: exact.
+ * ===================================================================== */
+typedef struct pcx_framer pcx_framer;
+enum { PCX_FRAME_OTHER = 0, PCX_FRAME_START = 1, PCX_FRAME_END = 2 };                       /* pcx_frame_event.kind */
+enum { PCX_SEG_INPUT = 0, PCX_SEG_POOL = 1, PCX_SEG_HEADER = 2, PCX_SEG_ZERO = 3 };         /* pcx_frame_segment.kind */
+#define PCX_FRAME_HEADER_BITS 58
+/* a label of the call, in the order of the port (ascending index).  kind: START when its id is the start id, else END when it is the
+ * end id, else OTHER.  length: the header's length field, already reduced modulo 65536 (FrameInsert.cpp:231-234: data * width when
+ * the data converts to size_t, else 0); ignored without a header */
+typedef struct pcx_frame_event {
+    uint64_t index, width;
+    uint32_t kind, length;
+} pcx_frame_event;
+/* one run of the output, in elements; it ends where the next entry begins.  src: INPUT the input element, POOL the element of the
+ * sync word (the preamble with every symbol repeated), HEADER the index of the frame's word of header bits, ZERO nothing */
+typedef struct pcx_frame_segment {
+    uint64_t dst, src;
+    uint32_t kind, reserved;
+} pcx_frame_segment;
+typedef struct pcx_frame_plan {
+    uint64_t consumed;        /* input elements the call consumes */
+    uint64_t used_events;     /* events the call handled: each is consumed with the input */
+    uint64_t out_len;         /* output elements */
+    uint64_t n_segments;      /* entries of the table, the sentinel {out_len, 0, ZERO} included */
+    uint64_t n_headers;       /* words of header bits: one per start event when a header follows */
+    int cut;                  /* the capacity ended the call in front of an event */
+} pcx_frame_plan;
+/* (scalar, is_complex) in {(PCX_U8, 0), (PCX_F32, 1), (PCX_F64, 1)}, anything else is PCX_ERR_ARG "unsupported type".  Preamble {1},
+ * symbol width 1, no header, header id 0x55, padding 0. */
+PCX_API int pcx_framer_create(pcx_framer **out, int scalar, int is_complex);
+PCX_API int pcx_framer_destroy(pcx_framer *h);
+/* count elements of the handle's type; an empty preamble and a symbol width of 0 are PCX_ERR_ARG (PreambleFramer.cpp:96,
+ * FrameInsert.cpp:120, :142), as is a header on a byte stream.  The sync word is uploaded where a device can be reached, else at
+ * the first call that computes. */
+PCX_API int pcx_framer_set_preamble(pcx_framer *h, const void *symbols, size_t count, size_t symbol_width, int with_header);
+PCX_API int pcx_framer_get_preamble(const pcx_framer *h, void *symbols, size_t cap, size_t *count, size_t *symbol_width, int *with_header);
+PCX_API int pcx_framer_set_header_id(pcx_framer *h, unsigned char id);
+PCX_API int pcx_framer_get_header_id(const pcx_framer *h, unsigned char *id);
+PCX_API int pcx_framer_set_padding(pcx_framer *h, size_t elements);
+PCX_API int pcx_framer_get_padding(const pcx_framer *h, size_t *elements);
+/* output BYTES a workgroup writes (a multiple of 16: the seams a test wants to straddle) and the longest slice of the segment table
+ * a workgroup keeps on chip */
+PCX_API int pcx_framer_get_geometry(size_t *tile_bytes, size_t *lds_segments);
+/* time sync 0, 1, then the seven Hamming(8,4) words: bit i of *bits is the i-th header symbol's bit.  Twelve bits of the length are
+ * coded, the checksum covers all sixteen (FrameHelper.hpp). */
+PCX_API int pcx_frame_header_bits(unsigned id, unsigned length, uint64_t *bits);
+/* HOST ONLY, no device is touched: what a call on n_in input elements with room for out_cap output elements does.  used, insert_at
+ * and shift (each NULL or n_events long) receive per event: whether the call handles it; where its insert begins in the output (an
+ * OTHER event: where its label lands); what the block adds to the label's index.  segs / header_words receive the first seg_cap /
+ * hdr_cap entries.  The walk is the reference's, with two differences: an event whose head would end in front of what
+ * is already passed on has an empty head; and the output is bounded -- events are taken in groups (an event and those behind it at
+ * the same index or in front of what the group passed on), a group whole and with the element its last label sits on, the call ends
+ * in front of the first group that does not fit (or at the capacity), and a group that exceeds an empty output buffer is PCX_ERR_ARG
+ * with both sizes in the message. */
+PCX_API int pcx_framer_plan(const pcx_framer *h, size_t n_in, size_t out_cap, const pcx_frame_event *events, size_t n_events, pcx_frame_plan *plan,
+                            unsigned char *used, uint64_t *insert_at, uint64_t *shift, pcx_frame_segment *segs, size_t seg_cap,
+                            uint64_t *header_words, size_t hdr_cap);
+/* plans and runs: out receives plan->out_len elements.  in and the out_cap elements of out must not share a byte (PCX_ERR_ARG
+ * "overlaps").  The events are host memory in both forms.  process takes host pointers (staged, or in place when page-locked);
+ * process_dev takes device pointers and enqueues on `stream`: the table is uploaded from host memory behind the stream, and the
+ * HOST waits for the call before the previous one where it reuses that call's table slot.  Unlike the calls of the other handles it
+ * can therefore NOT be captured into a graph: a captured stream has no host plan to run again and no event to wait for. */
+PCX_API int pcx_framer_process(pcx_framer *h, const void *in, size_t n_in, const pcx_frame_event *events, size_t n_events, void *out, size_t out_cap,
+                               pcx_frame_plan *plan, unsigned char *used, uint64_t *insert_at, uint64_t *shift);
+PCX_API int pcx_framer_process_dev(pcx_framer *h, const void *in_dev, size_t n_in, const pcx_frame_event *events, size_t n_events, void *out_dev,
+                                   size_t out_cap, pcx_frame_plan *plan, unsigned char *used, uint64_t *insert_at, uint64_t *shift, void *stream);
+
+/* ===================================================================== *
  *  /comms/symbol_mapper      digital/SymbolMapper.cpp
  *
  *  out[i] = map[in[i] & mask] (:89-91): one unsigned char in, one element of the stream type out.  Exact.

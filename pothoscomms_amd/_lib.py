@@ -26,6 +26,9 @@ REPACK_BITS_TO_SYMBOLS, REPACK_SYMBOLS_TO_BITS, REPACK_BYTES_TO_SYMBOLS, REPACK_
 WAVE_CONST, WAVE_SINE, WAVE_RAMP, WAVE_SQUARE = 0, 1, 2, 3                       # pcx_waveform_table
 NOISE_UNIFORM, NOISE_NORMAL, NOISE_LAPLACE, NOISE_POISSON = 0, 1, 2, 3           # pcx_noise_table
 NOISE_ENTRIES = 4096
+FRAME_OTHER, FRAME_START, FRAME_END = 0, 1, 2                                    # pcx_frame_event.kind
+SEG_INPUT, SEG_POOL, SEG_HEADER, SEG_ZERO = 0, 1, 2, 3                           # pcx_frame_segment.kind
+FRAME_HEADER_BITS = 58
 
 
 class PcxError(RuntimeError):
@@ -60,6 +63,22 @@ def qformat_ptr(q):
     if not isinstance(q, QFormat):
         q = QFormat(*[int(v) for v in q])
     return C.byref(q)
+
+
+class FrameEvent(C.Structure):
+    """pcx_frame_event: a label of a framer call (include/pcx.h)."""
+    _fields_ = [("index", C.c_uint64), ("width", C.c_uint64), ("kind", C.c_uint32), ("length", C.c_uint32)]
+
+
+class FrameSegment(C.Structure):
+    """pcx_frame_segment: one run of a framer call's output, in elements."""
+    _fields_ = [("dst", C.c_uint64), ("src", C.c_uint64), ("kind", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FramePlan(C.Structure):
+    """pcx_frame_plan: what a framer call consumes and produces."""
+    _fields_ = [("consumed", C.c_uint64), ("used_events", C.c_uint64), ("out_len", C.c_uint64), ("n_segments", C.c_uint64),
+                ("n_headers", C.c_uint64), ("cut", C.c_int)]
 
 
 _vp, _sz, _i, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_double
@@ -182,6 +201,19 @@ SIGNATURES = {
     "pcx_threshold_process_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
     "pcx_threshold_states": (_i, [_vp, _vp, _sz, _vp]),
     "pcx_threshold_states_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "pcx_framer_create": (_i, [C.POINTER(_vp), _i, _i]),
+    "pcx_framer_destroy": (_i, [_vp]),
+    "pcx_framer_set_preamble": (_i, [_vp, _vp, _sz, _sz, _i]),
+    "pcx_framer_get_preamble": (_i, [_vp, _vp, _sz, _psz, _psz, C.POINTER(_i)]),
+    "pcx_framer_set_header_id": (_i, [_vp, C.c_ubyte]),
+    "pcx_framer_get_header_id": (_i, [_vp, C.POINTER(C.c_ubyte)]),
+    "pcx_framer_set_padding": (_i, [_vp, _sz]),
+    "pcx_framer_get_padding": (_i, [_vp, _psz]),
+    "pcx_framer_get_geometry": (_i, [_psz, _psz]),
+    "pcx_frame_header_bits": (_i, [C.c_uint, C.c_uint, C.POINTER(C.c_uint64)]),
+    "pcx_framer_plan": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz]),
+    "pcx_framer_process": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "pcx_framer_process_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "pcx_mapper_create": (_i, [_i, _i, C.POINTER(_vp)]),
     "pcx_mapper_destroy": (_i, [_vp]),
     "pcx_mapper_set_map": (_i, [_vp, _vp, _sz]),

@@ -34,13 +34,15 @@ _blib = None
 # libpcx_symbol_blocks.so (symbol_blocks.cpp: /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder,
 # /comms/differential_decoder), "repack" libpcx_repack_blocks.so (repack_blocks.cpp: /comms/bits_to_symbols, /comms/symbols_to_bits,
 # /comms/bytes_to_symbols, /comms/symbols_to_bytes), "waveform" libpcx_waveform_blocks.so (waveform_blocks.cpp: /comms/waveform_source,
-# /comms/noise_source), "utility" libpcx_utility_blocks.so (utility_blocks.cpp: /comms/threshold) -- one registry each, as Pothos loads
-# one module library per source directory
+# /comms/noise_source), "utility" libpcx_utility_blocks.so (utility_blocks.cpp: /comms/threshold), "framer" libpcx_framer_blocks.so
+# (framer_blocks.cpp: /comms/preamble_framer, /comms/frame_insert) -- one registry each, as Pothos loads one module library per source
+# directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
            "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so"),
-           "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so")}
+           "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so"),
+           "framer": os.path.join(_HERE, "libpcx_framer_blocks.so")}
 _mlibs = {}
 
 
@@ -279,6 +281,13 @@ class Block:
                 v = C.c_int64()
                 _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
             return v.value
+        if name == "setPreamble" and str(self.dtype).startswith("complex_"):      # /comms/frame_insert: std::vector<std::complex<T>>
+            t = np.ascontiguousarray(np.asarray(args[0]).astype(np.complex128).reshape(-1))
+            return _check_in(self._module, L.pcxb_call_taps(self._h, n, t.view(np.float64).ctypes.data_as(C.c_void_p), t.size, 1))
+        if name == "getPreamble" and str(self.dtype).startswith("complex_"):
+            buf, cnt = np.zeros(1 << 16, np.float64), C.c_size_t()
+            _check_in(self._module, L.pcxb_get_taps(self._h, n, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(cnt), 1))
+            return buf[:2 * cnt.value].view(np.complex128).copy()
         if name == "setPreamble":               # std::vector<unsigned char>
             v = np.ascontiguousarray(np.asarray(args[0], dtype=np.uint8).reshape(-1))
             return _check_in(self._module, L.pcxb_call_bytes(self._h, n, v.ctypes.data_as(C.c_void_p) if v.size else None, v.size))
@@ -288,7 +297,7 @@ class Block:
             return [int(b) for b in buf[:cnt.value]]
         if not args:   # getter
             if name in ("getThreshold", "getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
-                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus"):
+                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus", "getPaddingSize", "getSymbolWidth", "getHeaderId"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value

@@ -144,7 +144,8 @@ public:
         const bool toNumber = to == typeid(bool) || to == typeid(int) || to == typeid(long) || to == typeid(long long) ||
                               to == typeid(unsigned) || to == typeid(unsigned long) || to == typeid(unsigned long long) ||
                               to == typeid(float) || to == typeid(double) ||
-                              to == typeid(short) || to == typeid(signed char);      // utility/Threshold.cpp:71, int16_t and int8_t levels
+                              to == typeid(short) || to == typeid(signed char) ||    // utility/Threshold.cpp:71, int16_t and int8_t levels
+                              to == typeid(unsigned char);                           // digital/FrameInsert.cpp:130, the header id
         if (toNumber) return isNumber();
         if (to == typeid(DType)) return *_t == typeid(std::string);
         if (to == typeid(std::complex<double>)) return isNumber();

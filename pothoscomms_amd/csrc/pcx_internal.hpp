@@ -325,6 +325,17 @@ int launch_thr_slice(const ThrShape &p, const void *in, void *out, size_t m, con
 int launch_thr_empty(const ThrWork &w, uint64_t *counts_out, hipStream_t st);
 // the state after each of the m elements, one byte each; the carried state is the entry state of the first slice and stays as it is
 int launch_thr_states(const ThrShape &p, const void *in, size_t m, const ThrWork &w, int first, unsigned char *states, hipStream_t st);
+// (splice.hip) /comms/preamble_framer, /comms/frame_insert: one entry of the segment table as the kernel reads it
+struct SpliceSeg {
+    uint64_t dst;                           // first output byte
+    uint64_t src;                           // kind << 62 | first source byte (HEADER: index of the frame's bit word)
+};
+size_t splice_tile_bytes();                 // output bytes per workgroup
+size_t splice_lds_segments();               // the longest slice of the table a workgroup stages in LDS
+// `total` output bytes of elements of es bytes (1, 8, 16) from nseg segments with the sentinel {total, 0} behind them; sym: the last
+// preamble symbol (complex_float32 in the first 8 bytes)
+int launch_splice(size_t es, const void *in, const void *pool, const SpliceSeg *segs, size_t nseg, const uint64_t *headers, void *out, size_t total,
+                  const unsigned char sym[16], hipStream_t st);
 // (symbols.hip) /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder, /comms/differential_decoder
 struct DiffShape {
     int decode = 0;

@@ -690,6 +690,156 @@ class Threshold(_Handle):
         _lib.check(_lib.load().pcx_threshold_states_dev(self._h, _dev_ptr(x), n, _dev_ptr(states), _stream_ptr(stream)))
 
 
+class Framer(_Handle):
+    """pcx_framer_*: digital/PreambleFramer.cpp (uint8) and digital/FrameInsert.cpp (complex_float32, complex_float64) -- a preamble in
+    front of every start label, zero padding behind every end label, the labels of a call given as events (index, width, kind,
+    length) with kind in {"other", "start", "end"} or the FRAME_* codes.  The host plans the call, one kernel writes the
+    framed stream.  A call returns a FramerResult: the output, what was consumed, and per event whether it was used, where its insert
+    begins and the shift of its label."""
+    _destroy = "pcx_framer_destroy"
+    KINDS = {"other": _lib.FRAME_OTHER, "start": _lib.FRAME_START, "end": _lib.FRAME_END}
+
+    class Result:
+        def __init__(self, out, plan, used, insert_at, shift):
+            self.out, self.consumed, self.out_len, self.used_events, self.cut = out, plan.consumed, plan.out_len, plan.used_events, bool(plan.cut)
+            self.n_segments, self.n_headers = plan.n_segments, plan.n_headers
+            self.used, self.insert_at, self.shift = used.astype(bool), insert_at, shift
+
+    def __init__(self, dtype="uint8", preamble=(1,), symbol_width=1, header=False, header_id=0x55, padding=0):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, self.cplx = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_framer_create(C.byref(self._h), self.scalar, int(self.cplx)))
+        self.np_dtype = np.dtype(NP_SCALAR[self.scalar])
+        if tuple(np.atleast_1d(preamble).tolist()) != (1,) or symbol_width != 1 or header:
+            self.set_preamble(preamble, symbol_width, header)
+        if header_id != 0x55:
+            self.set_header_id(header_id)
+        if padding:
+            self.set_padding(padding)
+
+    def _typed(self, a, what):
+        """symbols or a stream as the handle's element type: (n,) uint8 resp. (n, 2) of the scalar type"""
+        if self.cplx:
+            a = np.asarray(a)
+            if a.ndim == 1:
+                a = a.astype(np.complex64 if self.scalar == F32 else np.complex128)
+            a = as_pairs(a)
+            if a.dtype != self.np_dtype or a.ndim != 2 or a.shape[1] != 2:
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "framer: %s %s%s for a %s block" % (what, a.dtype, a.shape, self.dtype))
+            return np.ascontiguousarray(a)
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.uint8 or a.ndim != 1:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "framer: %s %s%s for a %s block" % (what, a.dtype, a.shape, self.dtype))
+        return a
+
+    def set_preamble(self, preamble, symbol_width=1, header=False):
+        p = np.asarray(preamble)
+        p = self._typed(p.astype(np.uint8) if not self.cplx else p, "preamble")
+        _lib.check(_lib.load().pcx_framer_set_preamble(self._h, _np_ptr(p) if p.size else None, p.shape[0], int(symbol_width), int(bool(header))))
+
+    def preamble(self):
+        """(symbols, symbol_width, header)"""
+        n, w, hd = C.c_size_t(), C.c_size_t(), C.c_int()
+        _lib.check(_lib.load().pcx_framer_get_preamble(self._h, None, 0, C.byref(n), C.byref(w), C.byref(hd)))
+        out = np.zeros((n.value, 2) if self.cplx else n.value, self.np_dtype)
+        _lib.check(_lib.load().pcx_framer_get_preamble(self._h, _np_ptr(out), n.value, C.byref(n), C.byref(w), C.byref(hd)))
+        return out, w.value, bool(hd.value)
+
+    def set_header_id(self, header_id):
+        _lib.check(_lib.load().pcx_framer_set_header_id(self._h, int(header_id) & 0xFF))
+
+    def header_id(self):
+        v = C.c_ubyte()
+        _lib.check(_lib.load().pcx_framer_get_header_id(self._h, C.byref(v)))
+        return v.value
+
+    def set_padding(self, padding):
+        _lib.check(_lib.load().pcx_framer_set_padding(self._h, int(padding)))
+
+    def padding(self):
+        v = C.c_size_t()
+        _lib.check(_lib.load().pcx_framer_get_padding(self._h, C.byref(v)))
+        return v.value
+
+    @staticmethod
+    def geometry():
+        """(tile_bytes, lds_segments): the output bytes a workgroup writes and the longest slice of the segment table it keeps on chip"""
+        v = [C.c_size_t() for _ in range(2)]
+        _lib.check(_lib.load().pcx_framer_get_geometry(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @staticmethod
+    def header_bits(header_id, length):
+        """the 58 header bits as an int: bit i belongs to the i-th header symbol"""
+        v = C.c_uint64()
+        _lib.check(_lib.load().pcx_frame_header_bits(int(header_id), int(length), C.byref(v)))
+        return v.value
+
+    @classmethod
+    def events(cls, events):
+        """[(index, width, kind, length)] -> a ctypes array of pcx_frame_event (at least one entry long) and the count; such a pair
+        passes through (a caller that reuses its events builds them once)"""
+        if isinstance(events, tuple) and len(events) == 2 and isinstance(events[0], C.Array):
+            return events
+        arr = (_lib.FrameEvent * max(1, len(events)))()
+        for e, (index, width, kind, length) in zip(arr, events):
+            e.index, e.width, e.kind, e.length = int(index), int(width), cls.KINDS.get(kind, kind), int(length) & 0xFFFF
+        return arr, len(events)
+
+    @staticmethod
+    def _per_event(n):
+        return np.zeros(max(1, n), np.uint8), np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint64)
+
+    def plan(self, n_in, out_cap, events, tables=True):
+        """host only: (Result without output, segments [(dst, kind, src)] with the sentinel, header words); tables=False leaves the last
+        two out (None) and plans once"""
+        ev, n = self.events(events)
+        plan = _lib.FramePlan()
+        used, at, shift = self._per_event(n)
+        L = _lib.load()
+        if not tables:
+            _lib.check(L.pcx_framer_plan(self._h, n_in, out_cap, ev, n, C.byref(plan), _np_ptr(used), _np_ptr(at), _np_ptr(shift), None, 0, None, 0))
+            return self.Result(None, plan, used[:n], at[:n], shift[:n]), None, None
+        # an event leaves at most three segments (its head, the sync word, the header or the padding) and one header word; the tail and
+        # the sentinel are two more
+        segs = (_lib.FrameSegment * (3 * n + 2))()
+        hdr = np.zeros(max(1, n), np.uint64)
+        _lib.check(L.pcx_framer_plan(self._h, n_in, out_cap, ev, n, C.byref(plan), _np_ptr(used), _np_ptr(at), _np_ptr(shift), segs, 3 * n + 2,
+                                     _np_ptr(hdr), n))
+        return (self.Result(None, plan, used[:n], at[:n], shift[:n]), [(g.dst, g.kind, g.src) for g in segs[:plan.n_segments]],
+                [int(v) for v in hdr[:plan.n_headers]])
+
+    def process(self, x, events=(), out_cap=None, out=None):
+        """x: the stream as a numpy array; out_cap: room of the output in elements (default: what the whole input needs); out: an array
+        of the element type with room for out_cap elements"""
+        x = self._typed(x, "input")
+        ev, n = self.events(events)
+        if out_cap is None:
+            pre, w, hd = self.preamble()
+            out_cap = x.shape[0] + n * (pre.shape[0] * w + (_lib.FRAME_HEADER_BITS if hd else 0) + self.padding()) if out is None else out.shape[0]
+        shape = (max(1, out_cap), 2) if self.cplx else (max(1, out_cap),)
+        if out is None:
+            out = np.zeros(shape, self.np_dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == self.np_dtype and out.flags.c_contiguous and out.shape[0] >= out_cap and out.shape[1:] == shape[1:]):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "framer: out must be a contiguous %s array with room for out_cap elements" % self.np_dtype)
+        plan = _lib.FramePlan()
+        used, at, shift = self._per_event(n)
+        _lib.check(_lib.load().pcx_framer_process(self._h, _np_ptr(x) if x.shape[0] else None, x.shape[0], ev, n, _np_ptr(out), out_cap, C.byref(plan),
+                                                  _np_ptr(used), _np_ptr(at), _np_ptr(shift)))
+        return self.Result(out[:plan.out_len], plan, used[:n], at[:n], shift[:n])
+
+    def process_dev(self, x, n_in, events, out, out_cap, stream=None):
+        """device tensors x and out (torch, used as memory: out_cap elements of room from out's first byte); the events stay on the host.
+        Enqueues on the stream and returns the Result without output; nothing is synchronised"""
+        ev, n = self.events(events)
+        plan = _lib.FramePlan()
+        used, at, shift = self._per_event(n)
+        _lib.check(_lib.load().pcx_framer_process_dev(self._h, _dev_ptr(x) if n_in else None, n_in, ev, n, _dev_ptr(out), out_cap, C.byref(plan),
+                                                      _np_ptr(used), _np_ptr(at), _np_ptr(shift), _stream_ptr(stream)))
+        return self.Result(None, plan, used[:n], at[:n], shift[:n])
+
+
 class _SymbolMap(_Handle):
     """what pcx_mapper_* and pcx_slicer_* share: a map in the stream type's own element layout"""
     _family = None
