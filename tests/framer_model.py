@@ -11,7 +11,12 @@ the same rules: an event at or behind the end of the input is left alone; the sh
 the next event with a different index; an end event's head runs to index + width, clipped; a head never runs backwards; events are
 taken in groups that fit the capacity whole, with the element their last label sits on (include/pcx.h, pcx_framer_plan).
 
-The header coder comes with its decoder (single-bit correction per Hamming word), which a frame synchroniser will need too."""
+The header coder comes with its decoder (single-bit correction per Hamming word), which a frame synchroniser will need too.
+
+tests/golden/framer.npz (tests/golden/make_framer_golden.py; `golden_cases` unpacks it) holds what the reference's own blocks posted.
+Both formulations equal it wherever no head would run backwards.  Its header part pins `header_bits` to the reference's
+encodeHeaderWord and `header_decode` to its decodeHeaderWord on 756 words with no, one and two flipped bits: the pin a frame
+synchroniser's decoder can rely on."""
 import collections
 
 import numpy as np
@@ -267,3 +272,65 @@ def index_map(x, events, cfg, cap=None):
 def expected_labels(events, res):
     """(event position, output index) of the labels the block posts"""
     return [(i, events[i][0] + res.shift[i]) for i in range(len(events)) if res.used[i]]
+
+
+# ---- the recorded reference (tests/golden/framer.npz, written by tests/golden/make_framer_golden.py)
+GOLDEN_TYPES = ("uint8", "complex_float32", "complex_float64")
+DATA_KINDS = (None, "integer", "string")        # what a label carries: nothing, an unsigned integer, a string
+
+
+def golden_input(dtype, n):
+    """the rows of the n input elements of a recorded case: every element carries its own position.  Bytes are 2 + i % 251, complex
+    elements (i, -(i + 0.5))"""
+    i = np.arange(n)
+    if dtype == "uint8":
+        return rows((2 + i % 251).astype(np.uint8))
+    return rows(np.stack([i, -(i + 0.5)], axis=1).astype(np.float32 if dtype == "complex_float32" else np.float64))
+
+
+def golden_output(x, src_delta, literals):
+    """the recorded output rows from their compact form: src (the running sum of src_delta) names the input row an output row equals,
+    -1 stands for the next of the literal rows"""
+    src = np.cumsum(src_delta, dtype=np.int64)
+    out = np.zeros((src.size, x.shape[1]), np.uint8)
+    out[src >= 0] = x[src[src >= 0]]
+    out[src < 0] = literals
+    return out
+
+
+def label_events(labels, start_id, end_id):
+    """[(id, index, width, data)] -> events, by the blocks' rules: the start id is tested before the end id; the header's length is
+    data * width cut to sixteen bits where the data is an integer, else 0"""
+    return [(index, width, "start" if i == start_id else "end" if i == end_id else "other", (data * width) & 0xFFFF if isinstance(data, int) else 0)
+            for i, index, width, data in labels]
+
+
+def golden_cases(path):
+    """-> (tile bytes, [case], header): a case is a dict of name, dtype, n, x (rows), preamble (as the element type: (P,) uint8 or (P, 2)),
+    cfg (a Config), start_id, end_id, labels [(id, index, width, data)], events, backward, leaves (the reference posted a chunk that
+    leaves its input: nothing else is recorded), consumed, out (rows) and posted [(place of the input label, index, width, kind of data)].
+    header holds the header coder's and decoder's recordings (see the maker).  These are the pin a frame synchroniser's decoder can rely
+    on: dec rows are (word, id, twelve length bits, checksum, error flag) of the reference's decodeHeaderWord."""
+    g = np.load(path)
+    lit = {t: g["lit_" + t] for t in GOLDEN_TYPES}
+    out = []
+    for k, (name, row) in enumerate(zip(g["names"].tolist(), g["case"].tolist())):
+        (tcode, n, width, hid, padding, P, pre_off, lab_off, n_lab, leaves, backward, consumed, out_rows, src_off, lit_off, n_lit, post_off, n_post) = row
+        t = GOLDEN_TYPES[tcode]
+        if t == "uint8":
+            pre = g["pre_u8"][pre_off:pre_off + P]
+        else:
+            pre = g["pre_c"][pre_off:pre_off + P].astype(np.float32 if t == "complex_float32" else np.float64)
+        labels = []
+        for j in range(lab_off, lab_off + n_lab):
+            index, w, kind, value = g["label_num"][j].tolist()
+            labels.append((str(g["label_id"][j]), index, w, None if kind == 0 else value if kind == 1 else str(g["label_text"][j])))
+        sid, eid = str(g["start_id"][k]), str(g["end_id"][k])
+        x = golden_input(t, n)
+        out.append(dict(name=name, dtype=t, n=n, x=x, preamble=pre, cfg=Config(rows(pre), width, t != "uint8", hid, padding), start_id=sid, end_id=eid,
+                        labels=labels, events=label_events(labels, sid, eid), backward=bool(backward), leaves=bool(leaves), consumed=consumed,
+                        out=golden_output(x, g["src"][src_off:src_off + out_rows], lit[t][lit_off:lit_off + n_lit]),
+                        posted=[tuple(p) for p in g["posted"][post_off:post_off + n_post].tolist()]))
+    header = dict(enc=[(i, ln, int(w)) for (i, ln), w in zip(g["enc_in"].tolist(), g["enc_word"].tolist())],
+                  enc_all=dict(zip(g["enc_all_id"].tolist(), g["enc_all_sha"].tolist())), dec=[tuple(int(v) for v in r) for r in g["dec"].tolist()])
+    return int(g["tile_bytes"]), out, header

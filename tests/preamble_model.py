@@ -1,7 +1,8 @@
 """Model of /comms/preamble_correlator (the reference's digital/PreambleCorrelator.cpp), the yardstick of tests/test_preamble_*.py.
 
-The reference block cannot be compiled without PothosCore, which is not available here, so there is no recorded output to compare
-with: the plain restatement of its loop below (`distances_plain`, `matches_plain`) IS the yardstick.  Three parts:
+The plain restatement of the reference's loop below (`distances_plain`, `matches_plain`) is held to tests/golden/preamble.npz, what the
+reference's own work() posted when compiled against a stand-in framework (tests/golden/make_preamble_golden.py; `golden_cases` unpacks
+it), and is the yardstick wherever no recording reaches.  Three parts:
 
   1. the reference's loop as it stands (PreambleCorrelator.cpp:134-151): for every position n < len(x) - P,
      dist = sum over i < P of popcount(preamble[i] ^ x[n + i]) through a 256-entry popcount table, O(N P), and a label at n + P
@@ -166,6 +167,40 @@ def plant(x, preamble, at):
     for a in at:
         x[a:a + pre.size] = pre
     return x
+
+
+def golden_stream(base, width, n, fill, mask, flip_at, flip_xor, preamble, at):
+    """a stream of tests/golden/preamble.npz: n symbols of the base array of that width (width 0: n times `fill`), the preamble planted at
+    `at`, then one symbol xor-ed where flip_at >= 0, then the mask or-ed over everything"""
+    x = np.full(n, fill, np.uint8) if width == 0 else base[width][:n].copy()
+    assert x.size == n
+    x = plant(x, preamble, at)
+    if flip_at >= 0:
+        x[flip_at] ^= flip_xor
+    return x | np.uint8(mask)
+
+
+def golden_cases(path):
+    """tests/golden/preamble.npz (make_preamble_golden.py) unpacked: (tile, halo, [case]) with a case a dict of name, preamble, x, at,
+    cuts (None for one work() on the whole stream per threshold) and calls: [(threshold, elements handed, consumed, reserve, forwarded,
+    label indices as uint64)]"""
+    g = np.load(path)
+    base = {1: g["base1"], 8: g["base8"]}
+    starts = np.concatenate([[0], np.cumsum(g["calls"][:, 6])])
+    assert starts[-1] == g["label_delta"].size
+    out = []
+    for name, row in zip(g["names"].tolist(), g["spec"].tolist()):
+        width, n, fill, mask, flip_at, flip_xor, pre_off, P, at_off, n_at, call_off, n_calls, is_cuts = row
+        pre = g["pre_all"][pre_off:pre_off + P]
+        at = g["at_all"][at_off:at_off + n_at].tolist()
+        calls = []
+        for k in range(call_off, call_off + n_calls):
+            thr, handed, consumed, reserve, forwarded, off, count = g["calls"][k].tolist()
+            assert off == starts[k]
+            calls.append((thr, handed, consumed, reserve, forwarded, np.cumsum(g["label_delta"][off:off + count], dtype=np.uint64)))
+        out.append(dict(name=name, preamble=pre, x=golden_stream(base, width, n, fill, mask, flip_at, flip_xor, pre, at), at=at,
+                        cuts=[c[1] - (p[1] - p[2]) for p, c in zip([(0, 0, 0)] + calls, calls)] if is_cuts else None, calls=calls))
+    return int(g["tile"]), int(g["halo"]), out
 
 
 def run_cuts(work, stream, cuts, P):

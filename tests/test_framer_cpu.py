@@ -532,3 +532,174 @@ def test_planner_header_alone_under_address_and_undefined_behaviour_sanitizers(t
     assert got[-2].startswith("%d %d 0 %d |" % (a.consumed, a.out_len, sum(a.used)))
     m = re.match(r"random 4000 plans, (\d+) errors, (\d+) cuts$", got[-1])
     assert m and int(m.group(2)) > 100, got[-1]
+
+
+# ---- the recorded reference: tests/golden/framer.npz, what the reference's own work() posted (tests/golden/make_framer_golden.py)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "framer.npz")
+# DESIGN.md 18, "a head never runs backwards": the recorded cases in which some start label's index, or some end label's index + width,
+# lies in front of what earlier labels have passed on.  There, and nowhere else, model and reference may differ: the reference's
+# `label.index - consumed` wraps.  An end label passes the element it sits on, so a start label behind it at the SAME index is such a case
+BACKWARD = sorted(
+    ["small/%s/%s" % (t, s) for t in M.GOLDEN_TYPES for s in ("end_width_overlaps_later_labels", "end_and_start_at_one_index")]
+    + ["seam/%s/start_end_start_%s" % (t, w) for t in M.GOLDEN_TYPES for w in ("first", "before_seam", "seam", "last")]
+    + ["backward/%s/ends_only" % t for t in M.GOLDEN_TYPES]
+    + ["backward/uint8/start_behind_an_end", "backward/uint8/end_ends_in_front_of_a_start"])
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return M.golden_cases(GOLDEN)
+
+
+def data_kind(data):
+    return M.DATA_KINDS.index(None if data is None else "integer" if isinstance(data, int) else "string")
+
+
+def posted_by(c, res):
+    """what the blocks post by the model's result, as the recording has it: (place of the input label, index, width, kind of data)"""
+    return [(k, at, c["labels"][k][2], data_kind(c["labels"][k][3])) for k, at in M.expected_labels(c["events"], res)]
+
+
+def equals_the_recording(c, out, consumed, posted):
+    return not c["leaves"] and consumed == c["consumed"] and posted == c["posted"] and out.shape == c["out"].shape and np.array_equal(out, c["out"])
+
+
+def backward_labels(c):
+    """the issue's rule, on the labels alone"""
+    passed, found = 0, []
+    for k, (index, width, kind, _) in enumerate(c["events"]):
+        if index >= c["n"]:
+            continue
+        if kind == "start":
+            found += [k] if index < passed else []
+            passed = max(passed, index)
+        elif kind == "end":
+            found += [k] if index + width < passed else []
+            passed = max(passed, min(index + width, c["n"]))
+    return found
+
+
+def test_both_formulations_equal_the_recorded_reference_except_on_the_backward_cases(golden):
+    _, cases, _ = golden
+    differ, ran = {"walk": [], "index_map": []}, 0
+    for c in cases:
+        for f in (M.walk, M.index_map):
+            out, res = f(c["x"], c["events"], c["cfg"])
+            assert res.error is None and not res.cut, c["name"]
+            if not equals_the_recording(c, out, res.consumed, posted_by(c, res)):
+                differ[f.__name__].append(c["name"])
+        ran += 1
+    assert ran == np.load(GOLDEN)["names"].size
+    backward = sorted(c["name"] for c in cases if c["backward"])
+    assert backward == sorted(c["name"] for c in cases if backward_labels(c))          # the maker's flag is the rule
+    assert sorted(differ["walk"]) == sorted(differ["index_map"]) == backward == BACKWARD
+    assert all(c["backward"] for c in cases if c["leaves"])
+
+
+def test_planner_equals_the_recorded_reference_on_every_case_that_is_not_backward(dev, golden):
+    _, cases, _ = golden
+    ran = 0
+    for c in cases:
+        if c["backward"]:
+            continue
+        cfg = c["cfg"]
+        f = dev.Framer(c["dtype"], c["preamble"], cfg.width, cfg.header, header_id=cfg.header_id, padding=cfg.padding)
+        cap = c["n"] + len(c["events"]) * (M.insert_len(cfg) + cfg.padding)
+        res, segs, words = f.plan(c["n"], cap, c["events"])
+        posted = [(k, c["events"][k][0] + int(res.shift[k]), c["labels"][k][2], data_kind(c["labels"][k][3])) for k in range(len(c["events"])) if res.used[k]]
+        assert not res.cut and res.out_len == c["out"].shape[0], c["name"]
+        assert equals_the_recording(c, run_table(c["x"], segs, words, cfg), res.consumed, posted), c["name"]
+        f.close()
+        ran += 1
+    assert ran == len(cases) - len(BACKWARD)
+
+
+def test_on_the_backward_cases_a_head_never_runs_backwards(golden):
+    """the backward label's head is empty, its insert goes where the output stands, and the input passes once, in order"""
+    _, cases, _ = golden
+    ran = 0
+    for c in cases:
+        if not c["backward"]:
+            continue
+        cfg, ev = c["cfg"], c["events"]
+        out, res = M.walk(c["x"], ev, cfg)
+        out2, res2 = M.index_map(c["x"], ev, cfg)
+        assert np.array_equal(out, out2) and res[:6] == res2[:6] and res.consumed == c["n"] and all(res.used), c["name"]
+        behind, stand, inserted = backward_labels(c), 0, np.zeros(out.shape[0], bool)
+        assert behind
+        for k, (index, width, kind, length) in enumerate(ev):
+            if kind == "other":
+                continue
+            rows_k = M.insert_rows(cfg, length) if kind == "start" else np.zeros((cfg.padding, out.shape[1]), np.uint8)
+            at = res.insert_at[k]
+            assert at >= stand and (at == stand) >= (k in behind), (c["name"], k)
+            assert np.array_equal(out[at:at + rows_k.shape[0]], rows_k), (c["name"], k)
+            inserted[at:at + rows_k.shape[0]] = True
+            stand = at + rows_k.shape[0]
+        assert np.array_equal(out[~inserted], c["x"]), c["name"]
+        ran += 1
+    assert ran == len(BACKWARD)
+
+
+def test_header_coder_and_decoder_equal_the_recorded_reference(dev, golden):
+    import hashlib
+    _, _, header = golden
+    assert len(header["enc"]) == 256 * 6 and {ln for _, ln, _ in header["enc"]} == {0, 1, 0x0FFF, 0x1000, 0xABCD, 0xFFFF}
+    for header_id, length, word in header["enc"]:
+        assert sum(b << i for i, b in enumerate(M.header_bits(header_id, length))) == word == dev.Framer.header_bits(header_id, length), (header_id, length)
+    assert sorted(header["enc_all"]) == [0x55, 0xA7]
+    for header_id, sha in header["enc_all"].items():
+        words = np.array([M.header_word(header_id, length) for length in range(65536)], dtype="<u8")
+        assert hashlib.sha256(words.tobytes()).hexdigest() == sha, header_id
+        assert np.array_equal(words, np.array([dev.Framer.header_bits(header_id, length) for length in range(65536)], dtype="<u8")), header_id
+    # per (id, length): the clean word, every single flipped bit (corrected, or one of the two sync bits) and flips of two bits
+    assert len(header["dec"]) == 6 * (1 + M.HEADER_BITS + 60 + 7)
+    for word, header_id, length, chk, error in header["dec"]:
+        assert M.header_decode([(word >> i) & 1 for i in range(M.HEADER_BITS)]) == (header_id, length, chk, bool(error)), hex(word)
+    errors = sum(r[4] for r in header["dec"])
+    assert len(header["dec"]) - errors >= 6 * (1 + M.HEADER_BITS) and errors >= 6 * 7 and max(r[2] for r in header["dec"]) <= 0xFFF
+
+
+def test_recorded_framer_fixture_covers_what_it_is_meant_to(golden):
+    tile_bytes, cases, header = golden
+    assert os.path.getsize(GOLDEN) <= 512 << 10 and tile_bytes == 16384
+    by = {c["name"]: c for c in cases}
+    assert len(by) == len(cases)
+    assert all(index < 1 << 31 for c in cases for _, index, _, _ in c["labels"])
+    # the scenarios above, on every type, with the ids that make their kinds
+    for t in M.GOLDEN_TYPES:
+        for name, (events, padding) in SCENARIOS.items():
+            c = by["small/%s/%s" % (t, name)]
+            assert c["events"] == [(i, w, k, ln if k == "start" else 0) for i, w, k, ln in events] and c["cfg"].padding == padding and c["n"] == N, c["name"]
+        assert (by["small/%s/equal_start_and_end_ids" % t]["start_id"], by["small/%s/equal_start_and_end_ids" % t]["end_id"]) == ("x", "x")
+        c = by["small/%s/empty_end_id_with_an_empty_id_label" % t]
+        assert c["end_id"] == "" and [l[0] for l in c["labels"]] == ["frameStart", "", "else"]
+        # three tiles and 37 elements; labels on the last element of a tile, on the first of the next and on the stream's last
+        tile = tile_bytes // c["x"].shape[1]
+        seam = [c for c in cases if c["name"].startswith("seam/%s/" % t)]
+        assert len(seam) == 20 and all(c["n"] == 3 * tile + 37 for c in seam)
+        for at in (0, tile - 1, tile, 3 * tile + 36):
+            for kind in ("start", "end"):
+                assert any(e[0] == at and e[2] == kind for c in seam if not c["backward"] for e in c["events"]), (t, at, kind)
+        assert by["seam/%s/insert_on_an_output_seam" % t]["posted"][1][:2] == (1, tile)      # an insert that begins on a seam of the output
+    assert [by["unit/P%d" % p]["preamble"].size for p in (1, 15, 16, 17, 33)] == [1, 15, 16, 17, 33]
+    for where in ("before_the_seam", "across_the_seam"):
+        c = by["run64/" + where]
+        idx = [e[0] for e in c["events"]]
+        assert len(idx) == 64 and idx == list(range(idx[0], idx[0] + 64)) and (idx[0] + 128 < tile_bytes) == (where == "before_the_seam")
+    # every kind of label and of label data is posted somewhere; the header's length field sees 0, 0xFFF, 0xABCD and a cut product
+    kinds = {(e[2], p[3]) for c in cases if not c["leaves"] for p in c["posted"] for e in [c["events"][p[0]]]}
+    assert kinds >= {(k, d) for k in ("start", "end", "other") for d in (0, 1, 2)}, kinds
+    for t in M.GOLDEN_TYPES[1:]:
+        negated_zero = 0
+        for last in ("1_0", "0_m2", "m0_3", "0_0"):
+            c = by["header/%s/%s" % (t, last)]
+            assert {e[3] for e in c["events"] if e[2] == "start"} == {0, 0xFFF, 0xABCD, (70000 * 3) & 0xFFFF} and (70000 * 3) >> 16
+            sym = c["cfg"].preamble[-1]
+            half = sym.size // 2
+            zero = [h for h in (0, 1) if not sym[h * half:(h + 1) * half].any()]        # components that are +0.0
+            minus = M.negated(sym)
+            assert (c["out"] == minus).all(axis=1).any() and (c["out"] == sym).all(axis=1).any()
+            negated_zero += len(zero)
+        assert negated_zero >= 3                                                          # (1, 0), (0, -2) and both of (0, 0)
+    assert len(cases) == 3 * len(SCENARIOS) + 3 * 20 + 5 + 2 + 8 + 5 + 1

@@ -3,6 +3,7 @@ blocks against the model (tests/framer_model.py), and the loopback into the prea
 bytes of the output, so that the sign of a zero counts.  Every test runs under a time limit of its own: when it expires the process
 ends there and nothing more is started on the device."""
 import faulthandler
+import os
 
 import numpy as np
 import pytest
@@ -283,3 +284,74 @@ def test_loopback_the_correlator_finds_every_frame_the_framer_made(dev):
     assert matches == len(starts) and positions == r.out_len - pre.size
     assert list(idx) == [int(at) + pre.size for at in r.insert_at] == [s + (k + 1) * pre.size for k, s in enumerate(starts)]
     f.close()
+
+
+# ---- the recorded reference: tests/golden/framer.npz, what the reference's own work() posted (tests/golden/make_framer_golden.py).
+# Every recorded case outside DESIGN.md 18's "a head never runs backwards" (the fixture's `backward` flag; tests/test_framer_cpu.py holds
+# the list of their names and that model and reference differ there and nowhere else)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "framer.npz")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return M.golden_cases(GOLDEN)
+
+
+def typed(rows, dtype):
+    return M.unrows(rows, None) if dtype == "uint8" else np.ascontiguousarray(rows).view(np.float32 if dtype == "complex_float32" else np.float64).reshape(-1, 2)
+
+
+def recorded_labels(c):
+    """what the reference posted, as the blocks' labels: (id, index, width, data)"""
+    assert all(c["labels"][k][2] == w and M.DATA_KINDS.index(None if c["labels"][k][3] is None else "integer" if isinstance(c["labels"][k][3], int) else "string") == kind
+               for k, _, w, kind in c["posted"])
+    return [(c["labels"][k][0], at, w, c["labels"][k][3]) for k, at, w, _ in c["posted"]]
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+def test_process_process_dev_and_the_blocks_equal_every_recorded_case_of_the_reference(dev, golden, dtype):
+    import torch
+    from pothoscomms_amd import blocks as B
+    tile_bytes, cases, _ = golden
+    assert dev.Framer.geometry()[0] == tile_bytes, "the kernel's output tile changed: record tests/golden/framer.npz again for the new tile"
+    mine = [c for c in cases if c["dtype"] == dtype]
+    assert mine and any(c["backward"] for c in mine)
+    header = dtype != "uint8"
+    blk = B.make("/comms/frame_insert", dtype, module="framer") if header else B.make("/comms/preamble_framer", module="framer")
+    es, ran = ES[dtype], 0
+    for c in mine:
+        if c["backward"]:
+            continue
+        cfg, ev, n, want = c["cfg"], c["events"], c["n"], c["out"]
+        x = typed(c["x"], dtype)
+        f = dev.Framer(dtype, c["preamble"], cfg.width, cfg.header, header_id=cfg.header_id, padding=cfg.padding)
+        # the host-pointer call
+        r = f.process(x, ev, out_cap=want.shape[0])
+        assert (r.consumed, r.out_len, r.cut) == (c["consumed"], want.shape[0], False), c["name"]
+        assert np.array_equal(M.rows(r.out), want), (c["name"], np.flatnonzero((M.rows(r.out) != want).any(axis=1))[:8])
+        posted = [(k, ev[k][0] + int(r.shift[k])) for k in range(len(ev)) if r.used[k]]
+        assert posted == [p[:2] for p in c["posted"]], c["name"]
+        # the device-pointer call, a canary behind the output
+        xd = torch.from_numpy(x).cuda()
+        outd = torch.full(((want.shape[0] + 8) * es,), CANARY, dtype=torch.uint8, device="cuda")
+        r = f.process_dev(xd, n, ev, outd, want.shape[0])
+        torch.cuda.synchronize()
+        got = outd.cpu().numpy().reshape(-1, es)
+        assert (r.consumed, r.out_len) == (c["consumed"], want.shape[0]) and np.array_equal(got[:want.shape[0]], want) and np.all(got[want.shape[0]:] == CANARY), c["name"]
+        assert [(k, ev[k][0] + int(r.shift[k])) for k in range(len(ev)) if r.used[k]] == posted, c["name"]
+        f.close()
+        # the block: its own classification of the ids and its own length field from the labels' data
+        pre = c["preamble"]
+        blk.call("setPreamble", np.ascontiguousarray(pre.astype(np.float64)).view(np.complex128).reshape(-1) if header else pre)
+        if header:
+            blk.call("setSymbolWidth", cfg.width)
+            blk.call("setHeaderId", cfg.header_id)
+        blk.call("setFrameStartId", c["start_id"])
+        blk.call("setFrameEndId", c["end_id"])
+        blk.call("setPaddingSize", cfg.padding)
+        out, consumed, made, _, labels = blk.work(x, want.shape[0], labels=post(B, c["labels"]), label_cap=max(64, len(ev)))
+        assert (consumed, made) == (c["consumed"], want.shape[0]) and np.array_equal(M.rows(out), want), c["name"]
+        assert [(l.id, l.index, l.width, l.data) for l in labels] == recorded_labels(c), c["name"]
+        ran += 1
+    blk.close()
+    assert ran == sum(not c["backward"] for c in mine)

@@ -297,3 +297,96 @@ def test_runner_exports_the_byte_vector_call_in_every_module():
                          capture_output=True, text=True, check=True).stdout
     exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
     assert {"pcxb_call_bytes", "pcxb_get_bytes", "pcxb_work"} <= exported
+
+
+# ---- the recorded reference: tests/golden/preamble.npz, what the reference's own work() posted (tests/golden/make_preamble_golden.py)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "preamble.npz")
+GOLDEN_LENGTHS = LENGTHS + [1027]
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return M.golden_cases(GOLDEN)
+
+
+def test_model_equals_every_recorded_call_of_the_reference(golden):
+    tile, halo, cases = golden
+    ran = 0
+    for c in cases:
+        pre, x, P = c["preamble"], c["x"], c["preamble"].size
+        if c["cuts"] is None:
+            d = M.distances_plain(pre, x)
+            assert np.array_equal(d, M.distances_planes(pre, x)), c["name"]
+            for thr, handed, consumed, reserve, forwarded, idx in c["calls"]:
+                want, N, nm = M.matches_plain(pre, thr, x)
+                assert (handed, consumed, forwarded, reserve) == (x.size, N, N, P + 1), (c["name"], thr)
+                assert nm == idx.size and np.array_equal(want, idx), (c["name"], thr)
+        else:
+            calls = iter(c["calls"])
+            thr = c["calls"][0][0]
+
+            def work(buf):
+                t, handed, consumed, reserve, forwarded, idx = next(calls)
+                want, N, nm = M.matches_plain(pre, thr, buf)
+                assert (t, handed, consumed, forwarded, reserve) == (thr, buf.size, N, N, P + 1), c["name"]
+                assert np.array_equal(want, idx), c["name"]
+                return N, want
+            labels, done = M.run_cuts(work, x, c["cuts"], P)
+            assert next(calls, None) is None
+            one_shot = M.matches_plain(pre, thr, x)
+            assert done == one_shot[1] and np.array_equal(labels, one_shot[0]), c["name"]
+        ran += 1
+    assert ran == np.load(GOLDEN)["names"].size == len(cases)
+
+
+def test_recorded_fixture_covers_what_it_is_meant_to(golden):
+    tile, halo, cases = golden
+    assert os.path.getsize(GOLDEN) <= 512 << 10
+    assert (tile, halo) == (4096, 1024)
+    by = {c["name"]: c for c in cases}
+    assert len(by) == len(cases)
+    for P in GOLDEN_LENGTHS:
+        for width in (1, 8):
+            c = by["grid/P%d/w%d" % (P, width)]
+            x, at = c["x"], c["at"]
+            assert c["preamble"].size == P and x.size == 3 * tile + 2 * P + 37 and int(x.max()) < 1 << width and int(c["preamble"].max()) < 1 << width
+            d = M.distances_plain(c["preamble"], x)
+            assert all(d[a] == 0 for a in at) and 0 in at and d.size - 1 in at            # every plant whole, the first and the last position
+            if P >= 2:
+                assert all(any(a < seam < a + P for a in at) for seam in (tile, 2 * tile)), P     # a plant across either seam
+            assert any(a + P == 2 * tile - P - 1 for a in at) or P >= tile // 4                   # right in front of a seam's window
+            assert [call[0] for call in c["calls"]] == sorted({0, 1, P, 8 * P - 1, 8 * P})
+            first, last = c["calls"][0], c["calls"][-1]
+            assert {a + P for a in at} <= set(first[5].tolist())                                  # threshold 0 finds the plants
+            assert np.array_equal(last[5], np.arange(P, x.size, dtype=np.uint64))                 # threshold 8 P matches everywhere
+            assert int(last[5][-1]) == x.size - 1 >= last[4] == x.size - P                        # labels run past the forwarded elements: no clamp
+    assert 1027 > halo >= 1024
+    for P in (6, 64, 257):
+        for pname in ("random", "zero", "ones"):
+            for fill in ("00", "ff"):
+                c = by["fill/P%d/%s/%s" % (P, pname, fill)]
+                assert c["x"].size == 2 * tile + P + 3 and c["x"].min() == c["x"].max() == int(fill, 16)
+                counts = [call[5].size for call in c["calls"]]
+                assert counts[-1] == c["x"].size - P and set(counts) <= {0, counts[-1]} and counts[0] in (0, counts[-1])
+    for width in (1, 2, 4, 8):
+        for P in (16, 100):
+            for where in ("lo", "hi"):
+                c, noisy = by["planes/w%d/P%d/%s" % (width, P, where)], by["planes/w%d/P%d/%s/noisy" % (width, P, where)]
+                active = int(np.bitwise_or.reduce(c["preamble"]))
+                assert bin(active).count("1") == width and (active & 1 if where == "lo" else active & 0x80)
+                d, dn = M.distances_plain(c["preamble"], c["x"]), M.distances_plain(c["preamble"], noisy["x"])
+                assert all(d[a] == 0 for a in c["at"]) and sorted(int(dn[a]) for a in c["at"]) == [0, 0, 2]
+    clean, dirty = by["dirty/clean"], by["dirty/dirty"]
+    assert np.array_equal(dirty["x"], clean["x"] | 0x80) and int(clean["x"].max()) == 1 and [call[0] for call in dirty["calls"]] == [0, 23, 24]
+    assert [call[5].size for call in dirty["calls"]][:2] == [0, 0] and np.array_equal(dirty["calls"][2][5], clean["calls"][0][5])
+    assert {124, 4114, 8024} <= set(clean["calls"][0][5].tolist())
+    for P in (6, 64, 200):
+        c = by["cuts/P%d" % P]
+        cuts = [1, P - 1, P, P, P + 1, 1, 2 * P, 5000, 3, 8192, P]
+        assert c["x"].size == 30000 and c["cuts"] == cuts + [30000 - sum(cuts)]
+        d = M.distances_plain(c["preamble"], c["x"])
+        assert all(d[a] == 0 for a in c["at"]) and len(c["at"]) == 6
+        # calls that could do nothing still ask for the reserve; others leave exactly a preamble's length unconsumed
+        assert [call[2] for call in c["calls"][:2]] == [0, 0] and all(call[3] == P + 1 for call in c["calls"])
+        assert all(call[1] - call[2] == P for call in c["calls"][2:])
+    assert len(cases) == 2 * len(GOLDEN_LENGTHS) + 18 + 32 + 2 + 3

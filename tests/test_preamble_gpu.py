@@ -2,6 +2,7 @@
 against the model (tests/preamble_model.py).  Every comparison is exact.  Every test runs under a time limit of its own: when it
 expires the process ends there and nothing more is started on the device."""
 import faulthandler
+import os
 
 import numpy as np
 import pytest
@@ -333,3 +334,68 @@ def test_graph_capture_replays_equal_to_the_eager_result(dev):
         e_idx, e_n, e_nm = c.process(x)                    # the eager call on the same input
         assert (e_n, e_nm) == (N, nm) and np.array_equal(e_idx, want)
     c.close()
+
+
+# ---- the recorded reference: tests/golden/preamble.npz, what the reference's own work() posted (tests/golden/make_preamble_golden.py)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "preamble.npz")
+FAMILIES = ["grid", "fill", "planes", "dirty", "cuts"]
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return M.golden_cases(GOLDEN)
+
+
+def test_recorded_cases_are_sorted_into_families_and_the_tile_is_the_recorded_one(dev, golden):
+    tile, halo, cases = golden
+    got_tile, _, longest = dev.PreambleCorrelator.geometry()
+    assert (got_tile, longest) == (tile, halo), "the kernel's tile or halo changed: record tests/golden/preamble.npz again for the new shapes"
+    assert {c["name"].split("/")[0] for c in cases} == set(FAMILIES)
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_process_distances_and_the_block_equal_every_recorded_call_of_the_reference(dev, golden, family):
+    from pothoscomms_amd import blocks as B
+    tile, halo, cases = golden
+    assert dev.PreambleCorrelator.geometry()[0] == tile, "record tests/golden/preamble.npz again for the new tile"
+    blk = B.make("/comms/preamble_correlator", module="correlator")
+    blk.call("setFrameStartId", "sof")
+    ran = 0
+    for case in cases:
+        if case["name"].split("/")[0] != family:
+            continue
+        pre, x, P = case["preamble"], case["x"], case["preamble"].size
+        c = dev.PreambleCorrelator(pre)
+        assert c.plan() == (dev._lib.PRE_BYTES if P > halo else dev._lib.PRE_PLANES)
+        blk.call("setPreamble", pre)
+
+        def check(buf, call, dist):
+            thr, handed, consumed, reserve, forwarded, want = call
+            assert handed == buf.size
+            # the distances decide the labels: positions at or under the threshold are the recorded ones, no other
+            assert dist.size == consumed and np.array_equal(np.flatnonzero(dist <= thr).astype(np.uint64) + np.uint64(P), want), (case["name"], thr)
+            c.set_threshold(thr)
+            idx, npos, nm = c.process(buf)
+            assert (npos, nm) == (consumed, want.size) and idx.dtype == np.uint64 and np.array_equal(idx, want), (case["name"], thr)
+            blk.call("setThreshold", thr)
+            got = block_labels(blk, buf, "sof")
+            assert got[:2] == (consumed, reserve) and consumed == forwarded, (case["name"], thr)
+            assert np.array_equal(np.array(got[2], np.uint64), want), (case["name"], thr)
+
+        if case["cuts"] is None:
+            dist = c.distances(x)
+            for call in case["calls"]:
+                check(x, call, dist)
+        else:
+            calls = iter(case["calls"])
+
+            def work(buf):
+                call = next(calls)
+                check(buf, call, c.distances(buf))
+                return call[2], call[5]
+            M.run_cuts(work, x, case["cuts"], P)
+            assert next(calls, None) is None
+        c.close()
+        ran += 1
+    blk.close()
+    assert ran == sum(c["name"].split("/")[0] == family for c in cases) > 0
