@@ -54,7 +54,8 @@
  *     per handle (every replay continues where the previous one ended).
  *   - the library reads no environment variable.
  *   - input and output buffers of one call must not overlap, with two exceptions the reference
- *     relies on or that cost nothing: the same-size element-wise maps (rotate, scale, conj, arith)
+ *     relies on or that cost nothing: the same-size element-wise maps (rotate, scale, conj, arith and the pcx_bitwise* / pcx_bitshift /
+ *     pcx_byteswap / pcx_arith_const family, whose other overlaps are refused with PCX_ERR_ARG)
  *     accept out == in exactly (Arithmetic forwards input 0's buffer, Arithmetic.cpp:157-158), and
  *     the FFT accepts out == in.  abs/angle (narrower output), FIR, FreqDemod and the fused chain
  *     read what another lane may already have overwritten: no aliasing.
@@ -78,7 +79,8 @@ extern "C" {
 
 typedef enum pcx_scalar {
     PCX_F64 = 0, PCX_F32 = 1, PCX_I64 = 2, PCX_I32 = 3, PCX_I16 = 4, PCX_I8 = 5,
-    /* unsigned element types: accepted by pcx_arith* only (arithmeticFactory, Arithmetic.cpp:284-296) */
+    /* unsigned element types: accepted by pcx_arith*, pcx_arith_const*, pcx_compare*, pcx_bitwise* and pcx_bitshift* only
+     * (arithmeticFactory, Arithmetic.cpp:284-296, and the factories of the blocks those calls serve) */
     PCX_U64 = 6, PCX_U32 = 7, PCX_U16 = 8, PCX_U8 = 9
 } pcx_scalar;
 
@@ -801,6 +803,42 @@ PCX_API int pcx_angle_dev(int scalar, const void *in_dev, void *out_dev, size_t 
 typedef enum pcx_arith_op { PCX_ARITH_ADD = 0, PCX_ARITH_SUB = 1, PCX_ARITH_MUL = 2, PCX_ARITH_DIV = 3 } pcx_arith_op;
 PCX_API int pcx_arith(int scalar, int is_complex, int op, const void *in0, const void *in1, void *out, size_t n);
 PCX_API int pcx_arith_dev(int scalar, int is_complex, int op, const void *in0_dev, const void *in1_dev, void *out_dev, size_t n, void *stream);
+/* ---- comparators, bitwise maps, byte order, arithmetic with a constant (logic.hip) ----
+ * Stateless, exact, one streaming pass each; every buffer may start at any element-aligned byte address.  A constant is passed as ONE
+ * element of the stream's type (two scalars for a complex stream).  Aliasing: `out` of a same-width map may be EXACTLY one of its
+ * inputs; a comparator's `out` may be its input only for the 1-byte types; any other overlap of the byte ranges is PCX_ERR_ARG and
+ * nothing is queued.  n == 0 returns PCX_OK without a launch.  Unknown op, type or width: PCX_ERR_ARG with a message.
+ *
+ * /comms/comparator, /comms/const_comparator (math/Comparator.cpp, math/ConstComparator.cpp): out[i] = (a[i] OP b[i]) ? 1 : 0 resp.
+ * (a[i] OP k) ? 1 : 0, one byte per scalar, the C++ operator of the type (all ten pcx_scalar codes): every ordered comparison and ==
+ * with a NaN gives 0, != gives 1, -0.0 == 0.0 gives 1. */
+typedef enum pcx_cmp_op { PCX_CMP_GT = 0, PCX_CMP_LT = 1, PCX_CMP_GE = 2, PCX_CMP_LE = 3, PCX_CMP_EQ = 4, PCX_CMP_NE = 5 } pcx_cmp_op;
+PCX_API int pcx_compare(int scalar, int op, const void *in0, const void *in1, void *out_u8, size_t n);
+PCX_API int pcx_compare_dev(int scalar, int op, const void *in0_dev, const void *in1_dev, void *out_u8_dev, size_t n, void *stream);
+PCX_API int pcx_compare_const(int scalar, int op, const void *in, const void *k, void *out_u8, size_t n);
+PCX_API int pcx_compare_const_dev(int scalar, int op, const void *in_dev, const void *k, void *out_u8_dev, size_t n, void *stream);
+/* /comms/bitwise_unary, /comms/bitwise_binary, /comms/const_bitwise_binary, /comms/bitshift (digital/Bitwise.cpp); the eight integer
+ * codes.  pcx_bitwise: NOT takes nin == 1; AND, OR, XOR fold nin >= 2 inputs in ONE pass of nin reads and one write (beyond eight
+ * inputs: further passes of `out` and up to seven more).  `out` may be ONE of the inputs, not two of them.  pcx_bitshift: << keeps the low bits, >> is arithmetic for the signed and
+ * logical for the unsigned types, as C++'s on the promoted value; a shift at or above the bit width is PCX_ERR_ARG. */
+typedef enum pcx_bit_op { PCX_BIT_NOT = 0, PCX_BIT_AND = 1, PCX_BIT_OR = 2, PCX_BIT_XOR = 3 } pcx_bit_op;
+PCX_API int pcx_bitwise(int scalar, int op, const void *const *ins, size_t nin, void *out, size_t n);
+PCX_API int pcx_bitwise_dev(int scalar, int op, const void *const *ins_dev, size_t nin, void *out_dev, size_t n, void *stream);
+PCX_API int pcx_bitwise_const(int scalar, int op, const void *in, const void *k, void *out, size_t n);
+PCX_API int pcx_bitwise_const_dev(int scalar, int op, const void *in_dev, const void *k, void *out_dev, size_t n, void *stream);
+PCX_API int pcx_bitshift(int scalar, int left, const void *in, size_t shift, void *out, size_t n);
+PCX_API int pcx_bitshift_dev(int scalar, int left, const void *in_dev, size_t shift, void *out_dev, size_t n, void *stream);
+/* /comms/byte_order (digital/ByteOrder.cpp, ByteOrder.hpp:109-114): each of the n_scalars scalars of `width` = 2, 4 or 8 bytes
+ * reversed; a complex element is two scalars */
+PCX_API int pcx_byteswap(int width, const void *in, void *out, size_t n_scalars);
+PCX_API int pcx_byteswap_dev(int width, const void *in_dev, void *out_dev, size_t n_scalars, void *stream);
+/* /comms/const_arithmetic (math/ConstArithmetic.cpp): pcx_arith's operators with the constant as one operand, the twenty element
+ * types.  Integer x / 0 yields 0 and MIN / -1 yields MIN, as in pcx_arith. */
+typedef enum pcx_arithk_op {
+    PCX_ARITHK_X_ADD_K = 0, PCX_ARITHK_X_SUB_K = 1, PCX_ARITHK_K_SUB_X = 2, PCX_ARITHK_X_MUL_K = 3, PCX_ARITHK_X_DIV_K = 4, PCX_ARITHK_K_DIV_X = 5
+} pcx_arithk_op;
+PCX_API int pcx_arith_const(int scalar, int is_complex, int op, const void *in, const void *k, void *out, size_t n);
+PCX_API int pcx_arith_const_dev(int scalar, int is_complex, int op, const void *in_dev, const void *k, void *out_dev, size_t n, void *stream);
 /* /comms/split_complex, /comms/combine_complex: utility/SplitComplex.cpp:10-18, utility/CombineComplex.cpp:10-17;
  * scalar = the real type of the planes (f64, f32, int64..int8: splitComplexFactory :60-70) */
 PCX_API int pcx_split_complex(int scalar, const void *in, void *re, void *im, size_t n);

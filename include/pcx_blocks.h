@@ -48,6 +48,18 @@ PCXB_API long pcxb_registry_arity(const char *path);
  *   fft: num_bins, inverse;  others: none */
 PCXB_API int pcxb_make(const char *path, const char *dtype, size_t dimension, const char *sarg, size_t num_bins,
                        int inverse, pcxb_block **out);
+/* BlockRegistry::make(path, dtype, args...) for the factories that take more than the above (the logic module's: an operation, a
+ * constant, a channel count, a shift size): one pcxb_arg per factory argument behind the dtype, in order.  A constant travels as
+ * PCXB_INT64 (the integer types; an unsigned 64-bit value by its bit pattern), PCXB_DOUBLE, or PCXB_COMPLEX (dval + i dim). */
+enum { PCXB_INT64 = 4, PCXB_COMPLEX = 5 };
+typedef struct pcxb_arg {
+    int kind;          /* PCXB_SIZE, PCXB_DOUBLE, PCXB_STRING, PCXB_INT64 or PCXB_COMPLEX */
+    uint64_t uval;
+    int64_t ival;
+    double dval, dim;
+    const char *sval;
+} pcxb_arg;
+PCXB_API int pcxb_make_args(const char *path, const char *dtype, size_t dimension, const pcxb_arg *args, size_t nargs, pcxb_block **out);
 PCXB_API int pcxb_destroy(pcxb_block *b);
 
 /* registered calls (registerCall names): one argument of the given kind, or a getter */

@@ -11,8 +11,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpcx_hip.so")
 
 # pcx_scalar
-F64, F32, I64, I32, I16, I8, U64, U32, U16, U8 = range(10)   # unsigned: pcx_arith* only
+F64, F32, I64, I32, I16, I8, U64, U32, U16, U8 = range(10)   # unsigned: pcx_arith*, pcx_arith_const*, pcx_compare*, pcx_bitwise*, pcx_bitshift* only
 ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV = range(4)
+CMP_GT, CMP_LT, CMP_GE, CMP_LE, CMP_EQ, CMP_NE = range(6)            # pcx_cmp_op
+BIT_NOT, BIT_AND, BIT_OR, BIT_XOR = range(4)                         # pcx_bit_op
+ARITHK_X_ADD_K, ARITHK_X_SUB_K, ARITHK_K_SUB_X, ARITHK_X_MUL_K, ARITHK_X_DIV_K, ARITHK_K_DIV_X = range(6)     # pcx_arithk_op
 # pcx_status
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4
 # pcx_fir_algo
@@ -276,6 +279,20 @@ SIGNATURES = {
     "pcx_angle_dev": (_i, [_i, _vp, _vp, _sz, _vp]),
     "pcx_arith": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz]),
     "pcx_arith_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pcx_compare": (_i, [_i, _i, _vp, _vp, _vp, _sz]),
+    "pcx_compare_dev": (_i, [_i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pcx_compare_const": (_i, [_i, _i, _vp, _vp, _vp, _sz]),
+    "pcx_compare_const_dev": (_i, [_i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pcx_bitwise": (_i, [_i, _i, C.POINTER(_vp), _sz, _vp, _sz]),
+    "pcx_bitwise_dev": (_i, [_i, _i, C.POINTER(_vp), _sz, _vp, _sz, _vp]),
+    "pcx_bitwise_const": (_i, [_i, _i, _vp, _vp, _vp, _sz]),
+    "pcx_bitwise_const_dev": (_i, [_i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pcx_bitshift": (_i, [_i, _i, _vp, _sz, _vp, _sz]),
+    "pcx_bitshift_dev": (_i, [_i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "pcx_byteswap": (_i, [_i, _vp, _vp, _sz]),
+    "pcx_byteswap_dev": (_i, [_i, _vp, _vp, _sz, _vp]),
+    "pcx_arith_const": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz]),
+    "pcx_arith_const_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "pcx_split_complex": (_i, [_i, _vp, _vp, _vp, _sz]),
     "pcx_split_complex_dev": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
     "pcx_combine_complex": (_i, [_i, _vp, _vp, _vp, _sz]),

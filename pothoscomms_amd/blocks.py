@@ -21,6 +21,31 @@ NONE, SIZE, DOUBLE, STRING = 0, 1, 2, 3
 _SIZE_MAX = C.c_size_t(-1).value
 
 
+class PcxbArg(C.Structure):
+    """pcxb_arg: one factory argument behind the dtype (pcxb_make_args)"""
+    _fields_ = [("kind", C.c_int), ("uval", C.c_uint64), ("ival", C.c_int64), ("dval", C.c_double), ("dim", C.c_double), ("sval", C.c_char_p)]
+
+
+INT64, COMPLEX = 4, 5
+
+
+def _factory_arg(a):
+    """a string, a count (int), or a constant of the stream's type given as a float, a complex or a numpy integer"""
+    c = PcxbArg()
+    if isinstance(a, str):
+        c.kind, c.sval = STRING, a.encode()
+    elif isinstance(a, (complex, np.complexfloating)):
+        c.kind, c.dval, c.dim = COMPLEX, float(a.real), float(a.imag)
+    elif isinstance(a, (float, np.floating)):
+        c.kind, c.dval = DOUBLE, float(a)
+    elif isinstance(a, np.integer) or (isinstance(a, int) and a < 0):
+        v = int(a)
+        c.kind, c.ival = INT64, v - (1 << 64) if v >= (1 << 63) else v
+    else:
+        c.kind, c.uval = SIZE, int(a)
+    return c
+
+
 class PcxbLabel(C.Structure):
     _fields_ = [("id", C.c_char * 32), ("index", C.c_uint64), ("width", C.c_uint64), ("kind", C.c_int),
                 ("uval", C.c_uint64), ("dval", C.c_double), ("sval", C.c_char * 32)]
@@ -35,14 +60,15 @@ _blib = None
 # /comms/differential_decoder), "repack" libpcx_repack_blocks.so (repack_blocks.cpp: /comms/bits_to_symbols, /comms/symbols_to_bits,
 # /comms/bytes_to_symbols, /comms/symbols_to_bytes), "waveform" libpcx_waveform_blocks.so (waveform_blocks.cpp: /comms/waveform_source,
 # /comms/noise_source), "utility" libpcx_utility_blocks.so (utility_blocks.cpp: /comms/threshold), "framer" libpcx_framer_blocks.so
-# (framer_blocks.cpp: /comms/preamble_framer, /comms/frame_insert) -- one registry each, as Pothos loads one module library per source
-# directory
+# (framer_blocks.cpp: /comms/preamble_framer, /comms/frame_insert), "logic" libpcx_logic_blocks.so (logic_blocks.cpp: /comms/comparator,
+# /comms/const_comparator, /comms/const_arithmetic, /comms/bitwise_unary, /comms/bitwise_binary, /comms/const_bitwise_binary,
+# /comms/bitshift, /comms/byte_order) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
            "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so"),
            "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so"),
-           "framer": os.path.join(_HERE, "libpcx_framer_blocks.so")}
+           "framer": os.path.join(_HERE, "libpcx_framer_blocks.so"), "logic": os.path.join(_HERE, "libpcx_logic_blocks.so")}
 _mlibs = {}
 
 
@@ -74,6 +100,7 @@ def load(module="comms"):
     L.pcxb_call_arity.restype = C.c_long
     L.pcxb_call_arity.argtypes = [vp, cp]
     L.pcxb_make.argtypes = [cp, cp, sz, cp, sz, i, C.POINTER(vp)]
+    L.pcxb_make_args.argtypes = [cp, cp, sz, C.POINTER(PcxbArg), sz, C.POINTER(vp)]
     L.pcxb_destroy.argtypes = [vp]
     L.pcxb_call_double.argtypes = [vp, cp, C.c_double]
     L.pcxb_call_size.argtypes = [vp, cp, sz]
@@ -195,7 +222,11 @@ class Block:
         elif path == "/comms/fft":
             nbins, inverse = int(args[0]), int(bool(args[1])) if len(args) > 1 else 0
         self._h = C.c_void_p()
-        _check_in(self._module, L.pcxb_make(path.encode(), (dtype or "").encode(), dimension, sarg, nbins, inverse, C.byref(self._h)))
+        if module == "logic":         # factories with an operation, a constant, a channel count or a shift size: pcxb_make_args
+            fargs = (PcxbArg * max(1, len(args)))(*[_factory_arg(a) for a in args])
+            _check_in(self._module, L.pcxb_make_args(path.encode(), (dtype or "").encode(), dimension, fargs, len(args), C.byref(self._h)))
+        else:
+            _check_in(self._module, L.pcxb_make(path.encode(), (dtype or "").encode(), dimension, sarg, nbins, inverse, C.byref(self._h)))
         self._slots = []          # blocks wired to this one's signals: kept alive as long as it can emit
         if path.endswith("fir_designer"):     # no stream ports: a signal source only
             self.in_dtype = self.out_dtype = None
@@ -281,6 +312,26 @@ class Block:
                 v = C.c_int64()
                 _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
             return v.value
+        if name == "setConstant":       # one element of the stream type (the logic module): complex, float, or an integer that keeps its 64 bits
+            if str(self.dtype).startswith("complex_"):
+                v = complex(args[0])
+                return _check_in(self._module, L.pcxb_call_complex(self._h, n, v.real, v.imag))
+            if str(self.dtype).startswith("float"):
+                return _check_in(self._module, L.pcxb_call_double(self._h, n, float(args[0])))
+            v = int(args[0])
+            return _check_in(self._module, L.pcxb_call_int64(self._h, n, v - (1 << 64) if v >= (1 << 63) else v))
+        if name == "constant" and not args:
+            if str(self.dtype).startswith("complex_"):
+                re, im = C.c_double(), C.c_double()
+                _check_in(self._module, L.pcxb_get_complex(self._h, n, C.byref(re), C.byref(im)))
+                return complex(re.value, im.value)
+            if str(self.dtype).startswith("float"):
+                v = C.c_double()
+                _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
+                return v.value
+            v = C.c_int64()
+            _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
+            return v.value + (1 << 64) if v.value < 0 and str(self.dtype).startswith("uint") else v.value
         if name == "setPreamble" and str(self.dtype).startswith("complex_"):      # /comms/frame_insert: std::vector<std::complex<T>>
             t = np.ascontiguousarray(np.asarray(args[0]).astype(np.complex128).reshape(-1))
             return _check_in(self._module, L.pcxb_call_taps(self._h, n, t.view(np.float64).ctypes.data_as(C.c_void_p), t.size, 1))
@@ -297,7 +348,7 @@ class Block:
             return [int(b) for b in buf[:cnt.value]]
         if not args:   # getter
             if name in ("getThreshold", "getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
-                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus", "getPaddingSize", "getSymbolWidth", "getHeaderId"):
+                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus", "getPaddingSize", "getSymbolWidth", "getHeaderId", "shiftSize"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value

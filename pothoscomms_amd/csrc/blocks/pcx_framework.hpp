@@ -22,6 +22,7 @@ namespace pcxfw = Pothos;
 #else
 
 #include <algorithm>
+#include <cctype>
 #include <complex>
 #include <cstdint>
 #include <cstdlib>
@@ -125,6 +126,9 @@ public:
     Object(const std::string &s) : _t(&typeid(std::string)), _s(s) {}
     Object(const DType &d) : _t(&typeid(DType)), _i((long long)d.dimension()), _s(d.name()) {}
     Object(const std::complex<double> &v) : _t(&typeid(std::complex<double>)), _d(v.real()), _im(v.imag()) {}     // waveform/WaveformSource.cpp:121
+    // math/ConstArithmetic.cpp:197, the constant of a complex stream: held as complex<double> (integer parts beyond 2^53 do not survive)
+    template <typename U>
+    Object(const std::complex<U> &v) : _t(&typeid(std::complex<double>)), _d((double)v.real()), _im((double)v.imag()) {}
     Object(const std::vector<double> &v) : _t(&typeid(std::vector<double>)), _vd(v) {}
     Object(const std::vector<std::complex<double>> &v) : _t(&typeid(std::vector<std::complex<double>>)), _vc(v) {}
     Object(const std::vector<size_t> &v) : _t(&typeid(std::vector<size_t>)), _vs(v) {}
@@ -145,8 +149,11 @@ public:
                               to == typeid(unsigned) || to == typeid(unsigned long) || to == typeid(unsigned long long) ||
                               to == typeid(float) || to == typeid(double) ||
                               to == typeid(short) || to == typeid(signed char) ||    // utility/Threshold.cpp:71, int16_t and int8_t levels
-                              to == typeid(unsigned char);                           // digital/FrameInsert.cpp:130, the header id
+                              to == typeid(unsigned char) ||                         // digital/FrameInsert.cpp:130, the header id
+                              to == typeid(unsigned short);                          // digital/Bitwise.cpp:400, a uint16_t constant
         if (toNumber) return isNumber();
+        if (to == typeid(Object)) return true;                                       // math/ConstArithmetic.cpp:232, a factory that takes an Object
+        if (isComplexType(to)) return isNumber() || *_t == typeid(std::complex<double>);      // :241, the constant of a complex stream
         if (to == typeid(DType)) return *_t == typeid(std::string);
         if (to == typeid(std::complex<double>)) return isNumber();
         if (to == typeid(std::vector<std::complex<double>>)) return *_t == typeid(std::vector<double>);
@@ -163,6 +170,19 @@ public:
     explicit operator T() const { return convert<T>(); }
 
 private:
+    static bool isComplexType(const std::type_info &to)
+    {
+        return to == typeid(std::complex<float>) || to == typeid(std::complex<long>) || to == typeid(std::complex<int>) || to == typeid(std::complex<short>) ||
+               to == typeid(std::complex<signed char>) || to == typeid(std::complex<unsigned long>) || to == typeid(std::complex<unsigned>) ||
+               to == typeid(std::complex<unsigned short>) || to == typeid(std::complex<unsigned char>);
+    }
+    Object get(Object *) const { return *this; }
+    template <typename U>
+    std::complex<U> get(std::complex<U> *) const
+    {
+        const std::complex<double> z = get(static_cast<std::complex<double> *>(nullptr));
+        return std::complex<U>((U)z.real(), (U)z.imag());
+    }
     template <typename T>
     typename std::enable_if<std::is_arithmetic<T>::value, T>::type get(T *) const
     {
@@ -528,6 +548,21 @@ public:
         if (it == _signals.end()) throw Exception("Block::emitSignal(" + name + ")", "no such signal");
         const std::vector<Object> args{Object(a)...};
         for (const auto &d : it->second) d.first->call(d.second, args);
+    }
+    // Pothos::Block::registerProbe(name): the slot "probe<Name>" emits the signal "<name>Triggered" with what the call `name` returns
+    void registerProbe(const std::string &name)
+    {
+        std::string slot = "probe" + name;
+        if (name.size()) slot[5] = (char)std::toupper((unsigned char)name[0]);
+        const std::string signal = name + "Triggered";
+        registerSignal(signal);
+        _calls[slot] = [this, name, signal](const std::vector<Object> &args) {
+            if (!args.empty()) throw Exception("Block::call(probe " + name + ")", "wrong number of arguments");
+            const std::vector<Object> value{this->call(name)};
+            for (const auto &d : _signals[signal]) d.first->call(d.second, value);
+            return Object();
+        };
+        _callArity[slot] = 0;
     }
     // true from just before activate() until deactivate() returns, as the Pothos actor keeps it
     bool isActive() const { return _active; }

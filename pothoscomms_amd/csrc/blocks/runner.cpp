@@ -107,6 +107,25 @@ int pcxb_make(const char *path, const char *dtype, size_t dimension, const char 
         *out = b.release();
     });
 }
+int pcxb_make_args(const char *path, const char *dtype, size_t dimension, const pcxb_arg *fargs, size_t nargs, pcxb_block **out)
+{
+    return guarded([&] {
+        std::vector<Object> args;
+        args.push_back(Object(DType(std::string(dtype), dimension ? dimension : 1)));
+        for (size_t i = 0; i < nargs; i++) {
+            const pcxb_arg &a = fargs[i];
+            if (a.kind == PCXB_STRING) args.push_back(Object(std::string(a.sval ? a.sval : "")));
+            else if (a.kind == PCXB_SIZE) args.push_back(Object((unsigned long)a.uval));
+            else if (a.kind == PCXB_INT64) args.push_back(Object((long long)a.ival));
+            else if (a.kind == PCXB_DOUBLE) args.push_back(Object(a.dval));
+            else if (a.kind == PCXB_COMPLEX) args.push_back(Object(std::complex<double>(a.dval, a.dim)));
+            else throw InvalidArgumentException("pcxb_make_args(" + std::string(path) + ")", "unknown argument kind");
+        }
+        std::unique_ptr<pcxb_block> b(new pcxb_block());
+        b->blk.reset(BlockRegistry::make(path, args));
+        *out = b.release();
+    });
+}
 int pcxb_destroy(pcxb_block *b) { delete b; return PCX_OK; }
 long pcxb_registry_arity(const char *path) { return path ? BlockRegistry::arity(path) : -1L; }
 int pcxb_call_count(pcxb_block *b, size_t *count) { return guarded([&] { *count = b->blk->callArities().size(); }); }

@@ -1,5 +1,6 @@
 // pcx_fft_api.hip -- the extern "C" boundary (include/pcx.h), part 3: /comms/fft (pcx_fft_*), /comms/freq_demod
-// (pcx_freqdemod_*) and the stateless maps (rotate, scale, abs, conjugate, angle, arithmetic, split / combine complex).
+// (pcx_freqdemod_*) and the stateless maps (rotate, scale, abs, conjugate, angle, arithmetic, split / combine complex, and the
+// comparator / bitwise / byte-order / const-arithmetic family of logic.hip).
 // Host-side only.
 #include "pcx_host.hpp"
 #include "pcx_tables.hpp"
@@ -698,4 +699,235 @@ int pcx_combine_complex(int scalar, const void *re, const void *im, void *out, s
         PCX_TRY(launch_combine_complex(scalar, dre, dim, dout, n, ws->st));
     }
     return stage_out_end(out, 2 * b, ws->out, staged, ws->st);
+}
+
+/* ---- comparators, bitwise maps, byte order, arithmetic with a constant (logic.hip) ---- */
+// may a call read [in, in + in_bytes) and write [out, out + out_bytes): no byte shared, or (same_ok, equal lengths) the very same buffer
+static bool map_overlap_ok(const void *in, size_t in_bytes, const void *out, size_t out_bytes, bool same_ok)
+{
+    return buffers_ok(in, in_bytes, out, out_bytes, same_ok && in_bytes == out_bytes);
+}
+#define PCX_CHECK_OVERLAP(in, in_bytes, out, out_bytes, who) \
+    PCX_CHECK_ARG(map_overlap_ok(in, in_bytes, out, out_bytes, true), who ": the output overlaps an input without being that very buffer")
+
+static int compare_args(int scalar, int op, const char *who)
+{
+    PCX_CHECK_ARG(valid_arith_scalar(scalar), "%s: unsupported type (scalar %d)", who, scalar);
+    PCX_CHECK_ARG(op >= PCX_CMP_GT && op <= PCX_CMP_NE, "%s: unknown comparison %d", who, op);
+    return PCX_OK;
+}
+int pcx_compare_dev(int scalar, int op, const void *in0_dev, const void *in1_dev, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_TRY(compare_args(scalar, op, "comparator"));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in0_dev && in1_dev && out_dev, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in0_dev, b, out_dev, n, "comparator");
+    PCX_CHECK_OVERLAP(in1_dev, b, out_dev, n, "comparator");
+    return launch_compare(scalar, op, in0_dev, in1_dev, out_dev, n, as_stream(stream));
+}
+int pcx_compare(int scalar, int op, const void *in0, const void *in1, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_TRY(compare_args(scalar, op, "comparator"));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in0 && in1 && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in0, b, out, n, "comparator");
+    PCX_CHECK_OVERLAP(in1, b, out, n, "comparator");
+    MapWs *ws;
+    PCX_TRY(map_ws(&ws));
+    const void *d0, *d1; void *dout; bool staged;
+    PCX_TRY(stage_reserve(in1, b, ws->in2));
+    PCX_TRY(stage_reserve(out, n, ws->out));
+    PCX_TRY(stage_in(in0, b, ws->in, ws->st, &d0));
+    PCX_TRY(stage_in(in1, b, ws->in2, ws->st, &d1));
+    PCX_TRY(stage_out_begin(out, n, ws->out, &dout, &staged));
+    {
+        LinkBound shape(in0, in1, out);
+        PCX_TRY(launch_compare(scalar, op, d0, d1, dout, n, ws->st));
+    }
+    return stage_out_end(out, n, ws->out, staged, ws->st);
+}
+int pcx_compare_const_dev(int scalar, int op, const void *in_dev, const void *k, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_TRY(compare_args(scalar, op, "const comparator"));
+    PCX_CHECK_ARG(k, "const comparator: null constant");
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    PCX_CHECK_OVERLAP(in_dev, n * (size_t)scalar_bytes(scalar), out_dev, n, "const comparator");
+    return launch_compare_const(scalar, op, in_dev, k, out_dev, n, as_stream(stream));
+}
+int pcx_compare_const(int scalar, int op, const void *in, const void *k, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_TRY(compare_args(scalar, op, "const comparator"));
+    PCX_CHECK_ARG(k, "const comparator: null constant");
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in, b, out, n, "const comparator");
+    return run_host_map(in, out, b, n, [&](const void *di, void *dout, hipStream_t st) { return launch_compare_const(scalar, op, di, k, dout, n, st); });
+}
+
+static int bitwise_args(int scalar, int op, size_t nin, const char *who)
+{
+    PCX_CHECK_ARG(is_int_scalar(scalar), "%s: unsupported type (scalar %d): the integer types only", who, scalar);
+    PCX_CHECK_ARG(op >= PCX_BIT_NOT && op <= PCX_BIT_XOR, "%s: unknown operation %d", who, op);
+    PCX_CHECK_ARG(nin != 0, "%s: no input", who);
+    PCX_CHECK_ARG(op == PCX_BIT_NOT ? nin == 1 : nin >= 2, "%s: operation %d over %zu input(s)", who, op, nin);
+    return PCX_OK;
+}
+int pcx_bitwise_dev(int scalar, int op, const void *const *ins_dev, size_t nin, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_TRY(bitwise_args(scalar, op, nin, "bitwise"));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(ins_dev && out_dev, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    size_t same = 0;
+    for (size_t i = 0; i < nin; i++) {
+        PCX_CHECK_ARG(ins_dev[i], "null buffer");
+        PCX_CHECK_OVERLAP(ins_dev[i], b, out_dev, b, "bitwise");
+        same += ins_dev[i] == out_dev;
+    }
+    PCX_CHECK_ARG(same <= 1, "bitwise: the output is %zu of the inputs; it may be one", same);
+    return launch_bitwise(op, ins_dev, nin, out_dev, b, as_stream(stream));
+}
+int pcx_bitwise(int scalar, int op, const void *const *ins, size_t nin, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_TRY(bitwise_args(scalar, op, nin, "bitwise"));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(ins && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    size_t same = 0;
+    for (size_t i = 0; i < nin; i++) {
+        PCX_CHECK_ARG(ins[i], "null buffer");
+        PCX_CHECK_OVERLAP(ins[i], b, out, b, "bitwise");
+        same += ins[i] == out;
+    }
+    PCX_CHECK_ARG(same <= 1, "bitwise: the output is %zu of the inputs; it may be one", same);
+    // host buffers cross the link one at a time: input 0 (and 1) first, then every further input folded into the staged result, each
+    // transfer complete before the workspace it went through is used again
+    MapWs *ws;
+    PCX_TRY(map_ws(&ws));
+    const void *d0, *d1; void *dout; bool staged;
+    PCX_TRY(stage_reserve(ins[0], b, ws->in));
+    for (size_t i = 1; i < nin; i++) PCX_TRY(stage_reserve(ins[i], b, ws->in2));
+    PCX_TRY(stage_reserve(out, b, ws->out));
+    // (an output that IS a later input: that input goes first, as in launch_bitwise)
+    std::vector<const void *> order(ins, ins + nin);
+    for (size_t i = 1; i < nin; i++)
+        if (order[i] == out) { std::swap(order[0], order[i]); break; }
+    PCX_TRY(stage_in(order[0], b, ws->in, ws->st, &d0));
+    PCX_TRY(stage_out_begin(out, b, ws->out, &dout, &staged));
+    LinkBound shape(order[0], out);
+    if (nin == 1) PCX_TRY(launch_bitwise(op, &d0, 1, dout, b, ws->st));
+    for (size_t i = 1; i < nin; i++) {
+        PCX_TRY(stage_in(order[i], b, ws->in2, ws->st, &d1));
+        const void *pair[2] = {i == 1 ? d0 : dout, d1};
+        PCX_TRY(launch_bitwise(op, pair, 2, dout, b, ws->st));
+        if (i + 1 < nin) PCX_HIP(hipStreamSynchronize(ws->st));
+    }
+    return stage_out_end(out, b, ws->out, staged, ws->st);
+}
+int pcx_bitwise_const_dev(int scalar, int op, const void *in_dev, const void *k, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(is_int_scalar(scalar), "const bitwise: unsupported type (scalar %d): the integer types only", scalar);
+    PCX_CHECK_ARG(op >= PCX_BIT_AND && op <= PCX_BIT_XOR, "const bitwise: unknown operation %d", op);
+    PCX_CHECK_ARG(k, "const bitwise: null constant");
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in_dev, b, out_dev, b, "const bitwise");
+    return launch_bitwise_const(op, scalar_bytes(scalar), in_dev, k, out_dev, b, as_stream(stream));
+}
+int pcx_bitwise_const(int scalar, int op, const void *in, const void *k, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(is_int_scalar(scalar), "const bitwise: unsupported type (scalar %d): the integer types only", scalar);
+    PCX_CHECK_ARG(op >= PCX_BIT_AND && op <= PCX_BIT_XOR, "const bitwise: unknown operation %d", op);
+    PCX_CHECK_ARG(k, "const bitwise: null constant");
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in, b, out, b, "const bitwise");
+    return run_host_map(in, out, b, b, [&](const void *di, void *dout, hipStream_t st) { return launch_bitwise_const(op, scalar_bytes(scalar), di, k, dout, b, st); });
+}
+static int bitshift_args(int scalar, size_t shift)
+{
+    PCX_CHECK_ARG(is_int_scalar(scalar), "bitshift: unsupported type (scalar %d): the integer types only", scalar);
+    PCX_CHECK_ARG(shift < 8 * (size_t)scalar_bytes(scalar), "bitshift: a shift of %zu on a type of %d bits", shift, 8 * scalar_bytes(scalar));
+    return PCX_OK;
+}
+int pcx_bitshift_dev(int scalar, int left, const void *in_dev, size_t shift, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_TRY(bitshift_args(scalar, shift));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in_dev, b, out_dev, b, "bitshift");
+    return launch_bitshift(scalar, left != 0, in_dev, (unsigned)shift, out_dev, n, as_stream(stream));
+}
+int pcx_bitshift(int scalar, int left, const void *in, size_t shift, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_TRY(bitshift_args(scalar, shift));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in, b, out, b, "bitshift");
+    return run_host_map(in, out, b, b, [&](const void *di, void *dout, hipStream_t st) { return launch_bitshift(scalar, left != 0, di, (unsigned)shift, dout, n, st); });
+}
+int pcx_byteswap_dev(int width, const void *in_dev, void *out_dev, size_t n_scalars, void *stream)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(width == 2 || width == 4 || width == 8, "byte order: unsupported scalar width %d", width);
+    if (n_scalars == 0) return PCX_OK;
+    PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    const size_t b = n_scalars * (size_t)width;
+    PCX_CHECK_OVERLAP(in_dev, b, out_dev, b, "byte order");
+    return launch_byteswap(width, in_dev, out_dev, n_scalars, as_stream(stream));
+}
+int pcx_byteswap(int width, const void *in, void *out, size_t n_scalars)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(width == 2 || width == 4 || width == 8, "byte order: unsupported scalar width %d", width);
+    if (n_scalars == 0) return PCX_OK;
+    PCX_CHECK_ARG(in && out, "null buffer");
+    const size_t b = n_scalars * (size_t)width;
+    PCX_CHECK_OVERLAP(in, b, out, b, "byte order");
+    return run_host_map(in, out, b, b, [&](const void *di, void *dout, hipStream_t st) { return launch_byteswap(width, di, dout, n_scalars, st); });
+}
+static int arith_const_args(int scalar, int op, const void *k)
+{
+    PCX_CHECK_ARG(valid_arith_scalar(scalar), "const arithmetic: unsupported type (scalar %d)", scalar);
+    PCX_CHECK_ARG(op >= PCX_ARITHK_X_ADD_K && op <= PCX_ARITHK_K_DIV_X, "const arithmetic: unknown operation %d", op);
+    PCX_CHECK_ARG(k, "const arithmetic: null constant");
+    return PCX_OK;
+}
+int pcx_arith_const_dev(int scalar, int is_complex, int op, const void *in_dev, const void *k, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_TRY(arith_const_args(scalar, op, k));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    const size_t b = n * elem_bytes(scalar, is_complex != 0);
+    PCX_CHECK_OVERLAP(in_dev, b, out_dev, b, "const arithmetic");
+    return launch_arith_const(scalar, is_complex, op, in_dev, k, out_dev, n, as_stream(stream));
+}
+int pcx_arith_const(int scalar, int is_complex, int op, const void *in, const void *k, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_TRY(arith_const_args(scalar, op, k));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in && out, "null buffer");
+    const size_t b = n * elem_bytes(scalar, is_complex != 0);
+    PCX_CHECK_OVERLAP(in, b, out, b, "const arithmetic");
+    return run_host_map(in, out, b, b, [&](const void *di, void *dout, hipStream_t st) { return launch_arith_const(scalar, is_complex, op, di, k, dout, n, st); });
 }

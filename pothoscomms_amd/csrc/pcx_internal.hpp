@@ -46,6 +46,7 @@ inline int scalar_bytes(int s)
 }
 inline bool valid_scalar(int s) { return s >= PCX_F64 && s <= PCX_I8; }
 inline bool valid_arith_scalar(int s) { return s >= PCX_F64 && s <= PCX_U8; }   // + the unsigned types
+inline bool is_int_scalar(int s) { return s >= PCX_I64 && s <= PCX_U8; }
 inline bool is_float_scalar(int s) { return s == PCX_F64 || s == PCX_F32; }
 // Q (accumulator) width for an integer element type: FIRFilter.cpp:377-382,
 // Rotate.cpp:151-154, Scale.cpp:150-153
@@ -218,6 +219,15 @@ int launch_angle(int scalar, const void *in, void *out, size_t n, hipStream_t st
 int launch_arith(int scalar, int is_complex, int op, const void *in0, const void *in1, void *out, size_t n, hipStream_t st);
 int launch_split_complex(int scalar, const void *in, void *re, void *im, size_t n, hipStream_t st);
 int launch_combine_complex(int scalar, const void *re, const void *im, void *out, size_t n, hipStream_t st);
+// (logic.hip) comparators (n scalars in, n bytes out), bitwise maps over `bytes` bytes, shifts, byte reversal of n_scalars scalars of
+// `width` bytes, and arith.hip's operators with the constant k (one element of the stream's type) as one operand
+int launch_compare(int scalar, int op, const void *in0, const void *in1, void *out, size_t n, hipStream_t st);
+int launch_compare_const(int scalar, int op, const void *in, const void *k, void *out, size_t n, hipStream_t st);
+int launch_bitwise(int op, const void *const *ins, size_t nin, void *out, size_t bytes, hipStream_t st);
+int launch_bitwise_const(int op, int width, const void *in, const void *k, void *out, size_t bytes, hipStream_t st);
+int launch_bitshift(int scalar, bool left, const void *in, unsigned shift, void *out, size_t n, hipStream_t st);
+int launch_byteswap(int width, const void *in, void *out, size_t n_scalars, hipStream_t st);
+int launch_arith_const(int scalar, int is_complex, int op, const void *in, const void *k, void *out, size_t n, hipStream_t st);
 // (dc_removal.hip) /comms/dc_removal: the shape of a configured handle and its two paths
 struct DcrShape {
     int scalar = PCX_F32;

@@ -15,8 +15,12 @@ from . import _lib
 from ._lib import F64, F32, I64, I32, I16, I8, U64, U32, U16, U8  # noqa: F401  (re-exported)
 
 NP_SCALAR = {F64: np.float64, F32: np.float32, I64: np.int64, I32: np.int32, I16: np.int16, I8: np.int8,
-             U64: np.uint64, U32: np.uint32, U16: np.uint16, U8: np.uint8}   # unsigned: arithmetic only
+             U64: np.uint64, U32: np.uint32, U16: np.uint16, U8: np.uint8}   # unsigned: arithmetic, comparators, bitwise only
 ARITH_OPS = {"ADD": _lib.ARITH_ADD, "SUB": _lib.ARITH_SUB, "MUL": _lib.ARITH_MUL, "DIV": _lib.ARITH_DIV}
+CMP_OPS = {">": _lib.CMP_GT, "<": _lib.CMP_LT, ">=": _lib.CMP_GE, "<=": _lib.CMP_LE, "==": _lib.CMP_EQ, "!=": _lib.CMP_NE}
+BIT_OPS = {"NOT": _lib.BIT_NOT, "AND": _lib.BIT_AND, "OR": _lib.BIT_OR, "XOR": _lib.BIT_XOR}
+ARITHK_OPS = {"X+K": _lib.ARITHK_X_ADD_K, "X-K": _lib.ARITHK_X_SUB_K, "K-X": _lib.ARITHK_K_SUB_X, "X*K": _lib.ARITHK_X_MUL_K,
+              "X/K": _lib.ARITHK_X_DIV_K, "K/X": _lib.ARITHK_K_DIV_X}
 SCALAR_OF_NP = {np.dtype(v): k for k, v in NP_SCALAR.items()}
 
 # Pothos DType names (DType::toString) -> (scalar code, is_complex)
@@ -1362,6 +1366,123 @@ def arith(op, a, b, is_complex, scalar=None, out=None, n=None, stream=None):
         raise ValueError("operands must match")
     y = np.zeros_like(a) if out is None else out
     _lib.check(L.pcx_arith(SCALAR_OF_NP[a.dtype], int(is_complex), ARITH_OPS[op], _np_ptr(a), _np_ptr(b), _np_ptr(y), a.shape[0]))
+    return y
+
+
+def _op_code(table, op, what):
+    if op not in table:
+        raise _lib.InvalidArgument(_lib.ERR_ARG, "%s: unknown operation %r" % (what, op))
+    return table[op]
+
+
+def _const_elem(k, scalar, is_complex=False):
+    """the constant as ONE element of the stream's type: a number, a complex number (complex streams), or an array that holds the element"""
+    dt = NP_SCALAR[scalar]
+    if isinstance(k, np.ndarray) and k.dtype == dt and k.size == (2 if is_complex else 1):
+        return np.ascontiguousarray(k).reshape(-1)
+    if is_complex:
+        k = complex(k) if np.isscalar(k) else complex(k[0], k[1])
+        return np.array([k.real, k.imag]).astype(dt)
+    return np.array([k]).astype(dt)
+
+
+def compare(op, a, b, scalar=None, out=None, n=None, stream=None):
+    """out[i] = (a[i] OP b[i]) ? 1 : 0 as uint8, OP in ">" "<" ">=" "<=" "==" "!=" (math/Comparator.cpp).  torch operands: device buffers of
+    n scalars of type `scalar`; numpy: host path."""
+    L, code = _lib.load(), _op_code(CMP_OPS, op, "comparator")
+    if _is_torch(a):
+        _lib.check(L.pcx_compare_dev(scalar, code, _dev_ptr(a), _dev_ptr(b), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        raise ValueError("operands must match")
+    y = np.zeros(a.size, dtype=np.uint8) if out is None else out
+    _lib.check(L.pcx_compare(SCALAR_OF_NP[a.dtype], code, _np_ptr(a), _np_ptr(b), _np_ptr(y), a.size))
+    return y
+
+
+def compare_const(op, x, k, scalar=None, out=None, n=None, stream=None):
+    """out[i] = (x[i] OP k) ? 1 : 0 as uint8 (math/ConstComparator.cpp); k is converted to the stream's type"""
+    L, code = _lib.load(), _op_code(CMP_OPS, op, "const comparator")
+    if _is_torch(x):
+        _lib.check(L.pcx_compare_const_dev(scalar, code, _dev_ptr(x), _np_ptr(_const_elem(k, scalar)), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    x = np.ascontiguousarray(x)
+    scalar = SCALAR_OF_NP[x.dtype]
+    y = np.zeros(x.size, dtype=np.uint8) if out is None else out
+    _lib.check(L.pcx_compare_const(scalar, code, _np_ptr(x), _np_ptr(_const_elem(k, scalar)), _np_ptr(y), x.size))
+    return y
+
+
+def bitwise(op, ins, scalar=None, out=None, n=None, stream=None):
+    """"NOT" of one input, or "AND" / "OR" / "XOR" folded over two inputs or more in one pass (digital/Bitwise.cpp); `out` may be one of them"""
+    L, code = _lib.load(), _op_code(BIT_OPS, op, "bitwise")
+    ins = [ins] if _is_torch(ins) or isinstance(ins, np.ndarray) else list(ins)
+    if ins and _is_torch(ins[0]):
+        ptrs = (C.c_void_p * len(ins))(*[_dev_ptr(t) for t in ins])
+        _lib.check(L.pcx_bitwise_dev(scalar, code, ptrs, len(ins), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    ins = [np.ascontiguousarray(a) for a in ins]
+    if any(a.shape != ins[0].shape or a.dtype != ins[0].dtype for a in ins):
+        raise ValueError("operands must match")
+    if not ins:
+        _lib.check(L.pcx_bitwise(U8 if scalar is None else scalar, code, None, 0, None, 0))
+    y = np.zeros_like(ins[0]) if out is None else out
+    ptrs = (C.c_void_p * len(ins))(*[a.ctypes.data for a in ins])
+    _lib.check(L.pcx_bitwise(SCALAR_OF_NP[ins[0].dtype], code, ptrs, len(ins), _np_ptr(y), ins[0].size))
+    return y
+
+
+def bitwise_const(op, x, k, scalar=None, out=None, n=None, stream=None):
+    """out[i] = x[i] OP k, OP in "AND" / "OR" / "XOR" (digital/Bitwise.cpp)"""
+    L, code = _lib.load(), _op_code(BIT_OPS, op, "const bitwise")
+    if _is_torch(x):
+        _lib.check(L.pcx_bitwise_const_dev(scalar, code, _dev_ptr(x), _np_ptr(_const_elem(k, scalar)), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    x = np.ascontiguousarray(x)
+    scalar = SCALAR_OF_NP[x.dtype]
+    y = np.zeros_like(x) if out is None else out
+    _lib.check(L.pcx_bitwise_const(scalar, code, _np_ptr(x), _np_ptr(_const_elem(k, scalar)), _np_ptr(y), x.size))
+    return y
+
+
+def bitshift(left, x, shift, scalar=None, out=None, n=None, stream=None):
+    """out[i] = x[i] << shift (left) or x[i] >> shift, as C++ on the promoted value (digital/Bitwise.cpp); shift below the bit width"""
+    L = _lib.load()
+    if shift < 0:
+        raise _lib.InvalidArgument(_lib.ERR_ARG, "bitshift: a negative shift")
+    if _is_torch(x):
+        _lib.check(L.pcx_bitshift_dev(scalar, int(bool(left)), _dev_ptr(x), int(shift), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    x = np.ascontiguousarray(x)
+    y = np.zeros_like(x) if out is None else out
+    _lib.check(L.pcx_bitshift(SCALAR_OF_NP[x.dtype], int(bool(left)), _np_ptr(x), int(shift), _np_ptr(y), x.size))
+    return y
+
+
+def byteswap(x, width=None, out=None, n=None, stream=None):
+    """every scalar of `width` = 2, 4 or 8 bytes reversed (digital/ByteOrder.hpp); n counts scalars, a complex element is two"""
+    L = _lib.load()
+    if _is_torch(x):
+        _lib.check(L.pcx_byteswap_dev(width, _dev_ptr(x), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    x = as_pairs(x)
+    y = np.zeros_like(x) if out is None else out
+    _lib.check(L.pcx_byteswap(x.dtype.itemsize if width is None else width, _np_ptr(x), _np_ptr(y), x.size))
+    return y
+
+
+def arith_const(op, x, k, is_complex, scalar=None, out=None, n=None, stream=None):
+    """out[i] = x[i] OP k or k OP x[i], op in "X+K" "X-K" "K-X" "X*K" "X/K" "K/X" (math/ConstArithmetic.cpp), the operators of arith()"""
+    L, code = _lib.load(), _op_code(ARITHK_OPS, op, "const arithmetic")
+    if _is_torch(x):
+        _lib.check(L.pcx_arith_const_dev(scalar, int(is_complex), code, _dev_ptr(x), _np_ptr(_const_elem(k, scalar, is_complex)), _dev_ptr(out), n,
+                                         _stream_ptr(stream)))
+        return out
+    x = as_pairs(x)
+    scalar = SCALAR_OF_NP[x.dtype]
+    y = np.zeros_like(x) if out is None else out
+    _lib.check(L.pcx_arith_const(scalar, int(is_complex), code, _np_ptr(x), _np_ptr(_const_elem(k, scalar, is_complex)), _np_ptr(y), x.shape[0]))
     return y
 
 
