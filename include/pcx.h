@@ -55,7 +55,7 @@
  *   - the library reads no environment variable.
  *   - input and output buffers of one call must not overlap, with two exceptions the reference
  *     relies on or that cost nothing: the same-size element-wise maps (rotate, scale, conj, arith and the pcx_bitwise* / pcx_bitshift /
- *     pcx_byteswap / pcx_arith_const family, whose other overlaps are refused with PCX_ERR_ARG)
+ *     pcx_byteswap / pcx_arith_const / pcx_mathfn family, whose other overlaps are refused with PCX_ERR_ARG)
  *     accept out == in exactly (Arithmetic forwards input 0's buffer, Arithmetic.cpp:157-158), and
  *     the FFT accepts out == in.  abs/angle (narrower output), FIR, FreqDemod and the fused chain
  *     read what another lane may already have overwritten: no aliasing.
@@ -839,6 +839,39 @@ typedef enum pcx_arithk_op {
 } pcx_arithk_op;
 PCX_API int pcx_arith_const(int scalar, int is_complex, int op, const void *in, const void *k, void *out, size_t n);
 PCX_API int pcx_arith_const_dev(int scalar, int is_complex, int op, const void *in_dev, const void *k, void *out_dev, size_t n, void *stream);
+/* ---- the real-valued function blocks (mathfn.hip): /comms/exp exp2 exp10 expm1 expN, /comms/log log2 log10 log1p logN, /comms/pow,
+ * /comms/sqrt cbrt nth_root, /comms/rsqrt, /comms/sinc, /comms/sigmoid, /comms/trigonometric (math/Exp.cpp, Log.cpp, Pow.cpp, Root.cpp,
+ * RSqrt.cpp, Sinc.cpp, Sigmoid.cpp, Trigonometric.cpp; the scalar loops).  PCX_F64 and PCX_F32 only; the reference's integer
+ * instantiations are not built and any other type is PCX_ERR_ARG ("unsupported type").
+ * Each code is ONE expression of the reference: reciprocal functions 1 / f(x), inverse reciprocal ones f(1 / x), SINC 1 where
+ * |x| < 1e-6 and sin(x) / x elsewhere, SIGMOID 1 / (1 + exp(-x)), EXPN pow(base, x), LOGN log(x) / log(base), POW pow(x, exponent),
+ * NTH_ROOT pow(x, 1.0 / root) resp. pow(x f, 1.0 / root) f with f = +-1 exactly when fmod(root, 2) == 1.  The choice the reference's
+ * setBase / setRoot make between these expressions (base 10 -> EXP10 / LOG10, root 3 -> CBRT, everything else generic, base 2 and
+ * root 2 included) is the block's, not this call's.
+ * Accuracy: float64 is the device library's function; float32 is the same double expression rounded once (within one unit in the
+ * last place of the correctly rounded value).  SQRT, and RSQRT in both types, are exact: RSQRT on float32 is the reference's bit-trick
+ * approximation (RSqrt.hpp), not 1 / sqrt.  Where the reference's float32 expression overflows INSIDE (sigmoid(-100), csch(90)) it
+ * returns 0 and this returns the small true value.
+ * `out` may be exactly `in`; any other overlap is PCX_ERR_ARG.  Buffers may start at any element-aligned byte address.  The codes
+ * from PCX_MATH_EXPN on take a parameter -- ONE value of the element type -- and go through pcx_mathfn_param; the others go through
+ * pcx_mathfn; either call refuses the other's codes.  A LOGN base <= 0 is PCX_ERR_ARG (Log.cpp:188-191).  Every refusal returns
+ * before a device is touched. */
+typedef enum pcx_math_fn {
+    PCX_MATH_EXP = 0, PCX_MATH_EXP2 = 1, PCX_MATH_EXP10 = 2, PCX_MATH_EXPM1 = 3,
+    PCX_MATH_LOG = 4, PCX_MATH_LOG2 = 5, PCX_MATH_LOG10 = 6, PCX_MATH_LOG1P = 7,
+    PCX_MATH_SQRT = 8, PCX_MATH_CBRT = 9, PCX_MATH_RSQRT = 10, PCX_MATH_SINC = 11, PCX_MATH_SIGMOID = 12,
+    /* /comms/trigonometric, in the order of its description */
+    PCX_MATH_COS = 16, PCX_MATH_SIN = 17, PCX_MATH_TAN = 18, PCX_MATH_SEC = 19, PCX_MATH_CSC = 20, PCX_MATH_COT = 21,
+    PCX_MATH_ACOS = 22, PCX_MATH_ASIN = 23, PCX_MATH_ATAN = 24, PCX_MATH_ASEC = 25, PCX_MATH_ACSC = 26, PCX_MATH_ACOT = 27,
+    PCX_MATH_COSH = 28, PCX_MATH_SINH = 29, PCX_MATH_TANH = 30, PCX_MATH_SECH = 31, PCX_MATH_CSCH = 32, PCX_MATH_COTH = 33,
+    PCX_MATH_ACOSH = 34, PCX_MATH_ASINH = 35, PCX_MATH_ATANH = 36, PCX_MATH_ASECH = 37, PCX_MATH_ACSCH = 38, PCX_MATH_ACOTH = 39,
+    /* with a parameter: base, base, exponent, root */
+    PCX_MATH_EXPN = 48, PCX_MATH_LOGN = 49, PCX_MATH_POW = 50, PCX_MATH_NTH_ROOT = 51
+} pcx_math_fn;
+PCX_API int pcx_mathfn(int scalar, int fn, const void *in, void *out, size_t n);
+PCX_API int pcx_mathfn_dev(int scalar, int fn, const void *in_dev, void *out_dev, size_t n, void *stream);
+PCX_API int pcx_mathfn_param(int scalar, int fn, const void *param, const void *in, void *out, size_t n);
+PCX_API int pcx_mathfn_param_dev(int scalar, int fn, const void *param, const void *in_dev, void *out_dev, size_t n, void *stream);
 /* /comms/split_complex, /comms/combine_complex: utility/SplitComplex.cpp:10-18, utility/CombineComplex.cpp:10-17;
  * scalar = the real type of the planes (f64, f32, int64..int8: splitComplexFactory :60-70) */
 PCX_API int pcx_split_complex(int scalar, const void *in, void *re, void *im, size_t n);

@@ -16,6 +16,13 @@ ARITH_ADD, ARITH_SUB, ARITH_MUL, ARITH_DIV = range(4)
 CMP_GT, CMP_LT, CMP_GE, CMP_LE, CMP_EQ, CMP_NE = range(6)            # pcx_cmp_op
 BIT_NOT, BIT_AND, BIT_OR, BIT_XOR = range(4)                         # pcx_bit_op
 ARITHK_X_ADD_K, ARITHK_X_SUB_K, ARITHK_K_SUB_X, ARITHK_X_MUL_K, ARITHK_X_DIV_K, ARITHK_K_DIV_X = range(6)     # pcx_arithk_op
+# pcx_math_fn: name -> code; the last four take a parameter (pcx_mathfn_param)
+MATH_FN = dict(zip(("EXP", "EXP2", "EXP10", "EXPM1", "LOG", "LOG2", "LOG10", "LOG1P", "SQRT", "CBRT", "RSQRT", "SINC", "SIGMOID"), range(13)))
+MATH_TRIG_OPS = ("COS", "SIN", "TAN", "SEC", "CSC", "COT", "ACOS", "ASIN", "ATAN", "ASEC", "ACSC", "ACOT",
+                 "COSH", "SINH", "TANH", "SECH", "CSCH", "COTH", "ACOSH", "ASINH", "ATANH", "ASECH", "ACSCH", "ACOTH")
+MATH_FN.update(zip(MATH_TRIG_OPS, range(16, 40)))
+MATH_FN.update(zip(("EXPN", "LOGN", "POW", "NTH_ROOT"), range(48, 52)))
+MATH_FN_PARAM = ("EXPN", "LOGN", "POW", "NTH_ROOT")
 # pcx_status
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4
 # pcx_fir_algo
@@ -293,6 +300,10 @@ SIGNATURES = {
     "pcx_byteswap_dev": (_i, [_i, _vp, _vp, _sz, _vp]),
     "pcx_arith_const": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz]),
     "pcx_arith_const_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pcx_mathfn": (_i, [_i, _i, _vp, _vp, _sz]),
+    "pcx_mathfn_dev": (_i, [_i, _i, _vp, _vp, _sz, _vp]),
+    "pcx_mathfn_param": (_i, [_i, _i, _vp, _vp, _vp, _sz]),
+    "pcx_mathfn_param_dev": (_i, [_i, _i, _vp, _vp, _vp, _sz, _vp]),
     "pcx_split_complex": (_i, [_i, _vp, _vp, _vp, _sz]),
     "pcx_split_complex_dev": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
     "pcx_combine_complex": (_i, [_i, _vp, _vp, _vp, _sz]),

@@ -62,13 +62,15 @@ _blib = None
 # /comms/noise_source), "utility" libpcx_utility_blocks.so (utility_blocks.cpp: /comms/threshold), "framer" libpcx_framer_blocks.so
 # (framer_blocks.cpp: /comms/preamble_framer, /comms/frame_insert), "logic" libpcx_logic_blocks.so (logic_blocks.cpp: /comms/comparator,
 # /comms/const_comparator, /comms/const_arithmetic, /comms/bitwise_unary, /comms/bitwise_binary, /comms/const_bitwise_binary,
-# /comms/bitshift, /comms/byte_order) -- one registry each, as Pothos loads one module library per source directory
+# /comms/bitshift, /comms/byte_order), "math" libpcx_math_blocks.so (math_blocks.cpp: /comms/exp, exp2, exp10, expm1, expN, log, log2, log10,
+# log1p, logN, pow, sqrt, cbrt, nth_root, rsqrt, sinc, sigmoid, trigonometric) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
            "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so"),
            "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so"),
-           "framer": os.path.join(_HERE, "libpcx_framer_blocks.so"), "logic": os.path.join(_HERE, "libpcx_logic_blocks.so")}
+           "framer": os.path.join(_HERE, "libpcx_framer_blocks.so"), "logic": os.path.join(_HERE, "libpcx_logic_blocks.so"),
+           "math": os.path.join(_HERE, "libpcx_math_blocks.so")}
 _mlibs = {}
 
 
@@ -222,7 +224,7 @@ class Block:
         elif path == "/comms/fft":
             nbins, inverse = int(args[0]), int(bool(args[1])) if len(args) > 1 else 0
         self._h = C.c_void_p()
-        if module == "logic":         # factories with an operation, a constant, a channel count or a shift size: pcxb_make_args
+        if module in ("logic", "math"):   # factories with an operation, a constant, a channel count, a shift size, a base, an exponent or a root: pcxb_make_args
             fargs = (PcxbArg * max(1, len(args)))(*[_factory_arg(a) for a in args])
             _check_in(self._module, L.pcxb_make_args(path.encode(), (dtype or "").encode(), dimension, fargs, len(args), C.byref(self._h)))
         else:
@@ -332,6 +334,12 @@ class Block:
             v = C.c_int64()
             _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
             return v.value + (1 << 64) if v.value < 0 and str(self.dtype).startswith("uint") else v.value
+        if name in ("setBase", "setExponent", "setRoot"):       # one value of the stream type (the math module)
+            return _check_in(self._module, L.pcxb_call_double(self._h, n, float(args[0])))
+        if name in ("base", "exponent", "root") and not args:
+            v = C.c_double()
+            _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
+            return v.value
         if name == "setPreamble" and str(self.dtype).startswith("complex_"):      # /comms/frame_insert: std::vector<std::complex<T>>
             t = np.ascontiguousarray(np.asarray(args[0]).astype(np.complex128).reshape(-1))
             return _check_in(self._module, L.pcxb_call_taps(self._h, n, t.view(np.float64).ctypes.data_as(C.c_void_p), t.size, 1))

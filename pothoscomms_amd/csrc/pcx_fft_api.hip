@@ -1,6 +1,6 @@
 // pcx_fft_api.hip -- the extern "C" boundary (include/pcx.h), part 3: /comms/fft (pcx_fft_*), /comms/freq_demod
 // (pcx_freqdemod_*) and the stateless maps (rotate, scale, abs, conjugate, angle, arithmetic, split / combine complex, and the
-// comparator / bitwise / byte-order / const-arithmetic family of logic.hip).
+// comparator / bitwise / byte-order / const-arithmetic family of logic.hip, the function family of mathfn.hip).
 // Host-side only.
 #include "pcx_host.hpp"
 #include "pcx_tables.hpp"
@@ -930,4 +930,73 @@ int pcx_arith_const(int scalar, int is_complex, int op, const void *in, const vo
     const size_t b = n * elem_bytes(scalar, is_complex != 0);
     PCX_CHECK_OVERLAP(in, b, out, b, "const arithmetic");
     return run_host_map(in, out, b, b, [&](const void *di, void *dout, hipStream_t st) { return launch_arith_const(scalar, is_complex, op, di, k, dout, n, st); });
+}
+
+/* ---- exp, log, pow, root, rsqrt, sinc, sigmoid, trigonometric (mathfn.hip) ---- */
+static bool mathfn_plain(int fn) { return (fn >= PCX_MATH_EXP && fn <= PCX_MATH_SIGMOID) || (fn >= PCX_MATH_COS && fn <= PCX_MATH_ACOTH); }
+static bool mathfn_with_param(int fn) { return fn >= PCX_MATH_EXPN && fn <= PCX_MATH_NTH_ROOT; }
+// every refusal of the family, before a device is touched; *p = the parameter widened (0 without one)
+static int mathfn_args(int scalar, int fn, bool with_param, const void *param, double *p)
+{
+    PCX_CHECK_ARG(is_float_scalar(scalar), "math function: unsupported type (scalar %d): float32 and float64 only", scalar);
+    PCX_CHECK_ARG(mathfn_plain(fn) || mathfn_with_param(fn), "math function: unknown function %d", fn);
+    *p = 0;
+    if (!with_param) {
+        PCX_CHECK_ARG(mathfn_plain(fn), "math function: function %d takes a parameter (pcx_mathfn_param)", fn);
+        return PCX_OK;
+    }
+    PCX_CHECK_ARG(mathfn_with_param(fn), "math function: function %d takes no parameter (pcx_mathfn)", fn);
+    PCX_CHECK_ARG(param, "math function: null parameter");
+    if (scalar == PCX_F32) {
+        float f;
+        std::memcpy(&f, param, sizeof f);
+        *p = f;
+    } else
+        std::memcpy(p, param, sizeof *p);
+    PCX_CHECK_ARG(fn != PCX_MATH_LOGN || !(*p <= 0), "Log base must be > 0");   // Log.cpp:188-191
+    return PCX_OK;
+}
+static int mathfn_dev(int scalar, int fn, double p, const void *in_dev, void *out_dev, size_t n, void *stream)
+{
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in_dev, b, out_dev, b, "math function");
+    return launch_mathfn(scalar, fn, p, in_dev, out_dev, n, as_stream(stream));
+}
+static int mathfn_host(int scalar, int fn, double p, const void *in, void *out, size_t n)
+{
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in, b, out, b, "math function");
+    return run_host_map(in, out, b, b, [&](const void *di, void *dout, hipStream_t st) { return launch_mathfn(scalar, fn, p, di, dout, n, st); });
+}
+int pcx_mathfn_dev(int scalar, int fn, const void *in_dev, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    double p;
+    PCX_TRY(mathfn_args(scalar, fn, false, nullptr, &p));
+    return mathfn_dev(scalar, fn, p, in_dev, out_dev, n, stream);
+}
+int pcx_mathfn(int scalar, int fn, const void *in, void *out, size_t n)
+{
+    PCX_TRACE();
+    double p;
+    PCX_TRY(mathfn_args(scalar, fn, false, nullptr, &p));
+    return mathfn_host(scalar, fn, p, in, out, n);
+}
+int pcx_mathfn_param_dev(int scalar, int fn, const void *param, const void *in_dev, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    double p;
+    PCX_TRY(mathfn_args(scalar, fn, true, param, &p));
+    return mathfn_dev(scalar, fn, p, in_dev, out_dev, n, stream);
+}
+int pcx_mathfn_param(int scalar, int fn, const void *param, const void *in, void *out, size_t n)
+{
+    PCX_TRACE();
+    double p;
+    PCX_TRY(mathfn_args(scalar, fn, true, param, &p));
+    return mathfn_host(scalar, fn, p, in, out, n);
 }

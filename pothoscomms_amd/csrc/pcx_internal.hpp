@@ -228,6 +228,8 @@ int launch_bitwise_const(int op, int width, const void *in, const void *k, void 
 int launch_bitshift(int scalar, bool left, const void *in, unsigned shift, void *out, size_t n, hipStream_t st);
 int launch_byteswap(int width, const void *in, void *out, size_t n_scalars, hipStream_t st);
 int launch_arith_const(int scalar, int is_complex, int op, const void *in, const void *k, void *out, size_t n, hipStream_t st);
+// (mathfn.hip) one function of pcx_math_fn over n float32 / float64 elements; `param` is the parameter of the codes from PCX_MATH_EXPN on
+int launch_mathfn(int scalar, int fn, double param, const void *in, void *out, size_t n, hipStream_t st);
 // (dc_removal.hip) /comms/dc_removal: the shape of a configured handle and its two paths
 struct DcrShape {
     int scalar = PCX_F32;

@@ -1460,6 +1460,32 @@ def bitshift(left, x, shift, scalar=None, out=None, n=None, stream=None):
     return y
 
 
+def math_fn(name, x, param=None, out=None, stream=None):
+    """out[i] = f(x[i]) for one function of pcx_math_fn, by name ("EXP" ... "SIGMOID", the 24 operations of /comms/trigonometric, and
+    with `param` "EXPN" (base), "LOGN" (base), "POW" (exponent), "NTH_ROOT" (root)); float32 and float64.  A numpy array goes the host
+    path, a device tensor stays on the device (`out` may be x itself; a new tensor by default)."""
+    L = _lib.load()
+    code = _op_code(_lib.MATH_FN, str(name).upper(), "math function")
+    if _is_torch(x):
+        import torch
+        scalar = {torch.float64: F64, torch.float32: F32}.get(x.dtype, I8)      # (any other type: refused by the call, as for numpy)
+        out = torch.empty_like(x) if out is None else out
+        ptrs, n, tail = (_dev_ptr(x), _dev_ptr(out)), x.numel(), (_stream_ptr(stream),)
+        host_fn, par_fn = L.pcx_mathfn_dev, L.pcx_mathfn_param_dev
+    else:
+        x = np.ascontiguousarray(x)
+        scalar = SCALAR_OF_NP.get(x.dtype, I8)
+        out = np.zeros_like(x) if out is None else out
+        ptrs, n, tail = (_np_ptr(x), _np_ptr(out)), x.size, ()
+        host_fn, par_fn = L.pcx_mathfn, L.pcx_mathfn_param
+    if param is None:
+        _lib.check(host_fn(scalar, code, *ptrs, n, *tail))
+    else:
+        k = np.array([param]).astype(NP_SCALAR[scalar] if scalar in (F64, F32) else np.float64)
+        _lib.check(par_fn(scalar, code, _np_ptr(k), *ptrs, n, *tail))
+    return out
+
+
 def byteswap(x, width=None, out=None, n=None, stream=None):
     """every scalar of `width` = 2, 4 or 8 bytes reversed (digital/ByteOrder.hpp); n counts scalars, a complex element is two"""
     L = _lib.load()
