@@ -252,6 +252,11 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
     const int variant = (int)PCX_ENV_INT("PCX_OLS_VARIANT", -1);
     const int align = (int)PCX_ENV_INT("PCX_OLS_ALIGN", 1);
 #ifdef PCX_DIAG
+    const bool one_near_row = PCX_ENV_INT("PCX_OLS_NEAR_ROWS", 2) == 1;     // the default policy with ONE normally cached row at either end of the window (below)
+#else
+    constexpr bool one_near_row = false;
+#endif
+#ifdef PCX_DIAG
     if (variant == 10 || variant == 11 || variant == 12 || variant == 13 || variant == 15 || variant == 16) {
         static bool warned = false;
         if (!warned) fprintf(stderr, "pcx(diag): PCX_OLS_VARIANT=%d selects a TIMING-ONLY build of the overlap-save FIR: its outputs are wrong\n", variant);
@@ -311,15 +316,19 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
 #else
     (void)variant; (void)g3; (void)gx;
 #endif
-    // non-temporal stores; non-temporal loads for the rows no other block reads; blocks dealt dynamically when the caller
-    // brought the counter pair (every pcx_fir handle does), else the grid stride
+    // non-temporal stores; non-temporal loads for the rows in the middle of the window; blocks dealt dynamically when the caller
+    // brought the counter pair (every pcx_fir handle does), else the grid stride.
+    // Up to Kov = 256 only rows 0 and 15 are shared with a neighbouring block, yet TWO rows at either end are cached normally
+    // (LAUX 5, the kernels of Kov <= 512): on the loads and stores alone of this launch shape that measured 0.1676 ms against
+    // 0.1764 with one row at either end (tools/floor_lab.hip `wide`, profiles/r07/floor_wide_rows.txt).
+    // PCX_OLS_NEAR_ROWS=1 (diag) brings the one-row policy back, for A/B
     if (dealt && gate.word) {
         // (Leaving a few of the 1024 resident slots empty, so that the kernels the gate waits for -- the halo's receive or copy, the
         // one-thread signal -- find room beside this launch, measured no better: 0.2196 ms at 1024 workgroups, 0.2242 at 1008,
         // two shards on one device, profiles/r03/shard_probe.txt.  PCX_GATED_SLOTS (diag) sets the number.)
         const long env_gd = PCX_ENV_INT("PCX_GATED_SLOTS", 0);
         const unsigned gd = env_gd > 0 ? (unsigned)env_gd : slots;
-        if (Kov <= 256) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 3, 0, false, true, 1>), gd);
+        if (Kov <= 256 && one_near_row) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 3, 0, false, true, 1>), gd);
         else if (Kov <= 512) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 5, 2, 3, 0, false, true, 1>), gd);
         else if (Kov <= 1024) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 6, 2, 3, 0, false, true, 1>), gd);
         else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 3, 0, false, true, 1>), gd);
@@ -332,12 +341,12 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
             else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 3>), gd);
         } else
 #endif
-        if (Kov <= 256) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 3, 0, false, false, 1>), gd);
+        if (Kov <= 256 && one_near_row) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 3, 0, false, false, 1>), gd);
         else if (Kov <= 512) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 5, 2, 3, 0, false, false, 1>), gd);
         else if (Kov <= 1024) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 6, 2, 3, 0, false, false, 1>), gd);
         else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 3, 0, false, false, 1>), gd);
     }
-    else if (Kov <= 256) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 0, false, false, 1>), g4);
+    else if (Kov <= 256 && one_near_row) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 0, false, false, 1>), g4);
     else if (Kov <= 512) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 5, 2, 0, 0, false, false, 1>), g4);
     else if (Kov <= 1024) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 6, 2, 0, 0, false, false, 1>), g4);
     else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 0, 0, false, false, 1>), g4);

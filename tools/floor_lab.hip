@@ -15,6 +15,7 @@
 // next to these rows by tools/floor_table.py through the product library, on the same box in the same call.
 //
 // Build: make -C tools floor_lab        Run: tools/floor_lab [seconds-per-row]
+//                                        tools/floor_lab <seconds-per-row> wide [rounds]: the headline's shape, 8- against 16-byte rows (below)
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -23,10 +24,13 @@
 #include <string>
 #include <vector>
 
+#include "../pothoscomms_amd/csrc/pcx_sched.hpp"
+
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
 typedef float cf __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, unsigned bytes)
 {
@@ -115,6 +119,122 @@ __global__ __launch_bounds__(256, OCC) void floor_kernel(const cf *__restrict__ 
     }
 }
 
+// ---- the headline's launch shape with 16-byte stream rows (profiles/r07/floor_wide_rows.txt) -----------------------------------
+// fir255 as the product runs it: 1024 workgroups, blocks DEALT (pcx_sched.hpp), S = 3840, the block's first 2 KiB row dropped by the
+// store descriptor's range check.  WIDE = false: sixteen 8-byte rows per lane, lane j on column j (the product's accesses).
+// WIDE = true: eight 16-byte accesses per lane, access k = rows 2k (lanes 0-31 of a wave) and 2k+1 (lanes 32-63) at columns
+// 64w + 2(l & 31) and the next; with SWAP the half-wave exchange that leaves every lane with both rows of ONE column
+// (v_permlane32_swap: vdst = the lane's first element, src = its second) is spent on the way in and on the way out, 32 per block.
+// NOV rows at either end of the window are cached normally, the rest nt: 1 = the product (only rows 0 and 15 are shared with a
+// neighbouring block), 2 = what a row PAIR can express, 4, 8 = every row.
+__device__ __forceinline__ void half_swap(cf &first, cf &second)
+{
+    unsigned a[2] = {__float_as_uint(first.x), __float_as_uint(first.y)}, b[2] = {__float_as_uint(second.x), __float_as_uint(second.y)};
+#pragma unroll
+    for (int d = 0; d < 2; d++) {
+        const auto r = __builtin_amdgcn_permlane32_swap(a[d], b[d], false, false);
+        a[d] = r[0]; b[d] = r[1];
+    }
+    first = cf{__uint_as_float(a[0]), __uint_as_float(a[1])};
+    second = cf{__uint_as_float(b[0]), __uint_as_float(b[1])};
+}
+
+template <bool WIDE, int NOV, int MODE, bool SWAP>     // MODE 0 mem, 1 dose
+__global__ __launch_bounds__(256, 4) void dealt_kernel(const cf *__restrict__ in, size_t in_elems, unsigned char *__restrict__ out, Shape s, float k,
+                                                      pcx::SchedState *__restrict__ sched)
+{
+    __shared__ cf lds[4608 + 64];
+    __shared__ unsigned sched_slot;
+    const int j = threadIdx.x, l = j & 63;
+    const cf c = {k, k};
+    if (j == 0) lds[0] = c;              // (the image is part of the shape: keep it allocated)
+    pcx::BlockDealer deal;
+    if (!deal.begin(sched, &sched_slot, s.nblocks, j)) { deal.finish(j); return; }
+    const int col = WIDE ? (j & ~63) + 2 * (l & 31) : j;
+    const int lane_off = WIDE ? col * 8 + (l >> 5) * 2048 : j * 8;
+    for (;;) {
+        const size_t b = deal.block();
+        cf v[16];
+        const size_t first = b * s.in_step;
+        const size_t left = in_elems - first;
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(in + first, (unsigned)((left < 4096 ? left : 4096) * 8));
+        if (WIDE) {
+#pragma unroll
+            for (int p = 0; p < 8; p++) {
+                const u32x4 t = (2 * p < NOV || 2 * p + 1 >= 16 - NOV) ? __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off, 4096 * p, 0)
+                                                   : __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off, 4096 * p, 2);
+                v[2 * p] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
+                v[2 * p + 1] = cf{__uint_as_float(t.z), __uint_as_float(t.w)};
+            }
+            if (SWAP) {
+#pragma unroll
+                for (int p = 0; p < 8; p++) half_swap(v[2 * p], v[2 * p + 1]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const bool plain = r < NOV || r >= 16 - NOV;
+                const u32x2 t = plain ? __builtin_amdgcn_raw_buffer_load_b64(rs, lane_off, 2048 * r, 0)
+                                      : __builtin_amdgcn_raw_buffer_load_b64(rs, lane_off, 2048 * r, 2);
+                v[r] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
+            }
+        }
+        asm volatile("" : : "v"(v[0]));      // row 0 is loaded as the product loads it, though none of it is stored
+        if (MODE >= 1) dose(v, 16, c);
+        deal.draw(j);
+        if (MODE >= 1) dose(v, s.valu - 16, c);
+        deal.publish(j);
+        __syncthreads();
+        // rows 1 .. 15 of the block are outputs b S .. b S + 3839; row 0 lies in front of the descriptor: its offsets wrap and are dropped
+        const size_t o0 = b * s.out_per_block;
+        const size_t room = s.nblocks * s.out_per_block - o0;      // (the lab's last block is a full one)
+        const __amdgpu_buffer_rsrc_t ws = make_rsrc(out + o0 * 8, (unsigned)((room < s.out_per_block ? room : s.out_per_block) * 8));
+        if (WIDE) {
+            if (SWAP) {
+#pragma unroll
+                for (int p = 0; p < 8; p++) half_swap(v[2 * p], v[2 * p + 1]);
+            }
+            const unsigned vbase = (unsigned)(lane_off - 2048);
+#pragma unroll
+            for (int p = 0; p < 8; p++)
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[2 * p].x), __float_as_uint(v[2 * p].y), __float_as_uint(v[2 * p + 1].x), __float_as_uint(v[2 * p + 1].y)},
+                                                       ws, (int)(vbase + 4096u * p), 0, 2);
+        } else {
+            const unsigned vbase = (unsigned)(lane_off - 2048);
+#pragma unroll
+            for (int r = 1; r < 16; r++)
+                __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(v[r].x), __float_as_uint(v[r].y)}, ws, (int)(vbase + 2048u * r), 0, 2);
+        }
+        if (!deal.advance()) break;
+        __syncthreads();                 // the slot is rewritten by the next block's publish
+    }
+    deal.finish(j);
+}
+
+template <bool WIDE, int NOV, int MODE, bool SWAP>
+static double run_dealt(const Shape &s, const cf *in, size_t in_elems, unsigned char *out, double seconds, float k, pcx::SchedState *sched)
+{
+    auto launch = [&]() { hipLaunchKernelGGL((dealt_kernel<WIDE, NOV, MODE, SWAP>), dim3(s.grid), dim3(256), 0, 0, in, in_elems, out, s, k, sched); };
+    for (int i = 0; i < 200; i++) launch();
+    CK(hipDeviceSynchronize());
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    int n = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    CK(hipEventRecord(e0, 0));
+    do {
+        for (int i = 0; i < 100; i++) launch();
+        n += 100;
+        CK(hipStreamSynchronize(0));
+    } while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds);
+    CK(hipEventRecord(e1, 0));
+    CK(hipEventSynchronize(e1));
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
+    return ms / n;
+}
+
 template <int OCC, int ROWS>
 static double run(const Shape &s, int mode, const cf *in, size_t in_elems, unsigned char *out, double seconds, float k)
 {
@@ -161,9 +281,9 @@ int main(int argc, char **argv)
     const Shape dc{"decim8 (255 taps, 64 Mi in)", 3, 729, 16, 3840, 8, 480, 4, 402, 3, (C + 3839) / 3840, 9.0 * C};
     const Shape ip{"interp4 (255 taps/phase, 16 Mi in)", 3, 729, 4, 768, 8, 3072, 4, 447, 3, (C / 4 + 767) / 768, 8.0 * (C / 4) + 8.0 * C};
     const Shape fr{"fir255 (255 taps, 64 Mi) for scale", 4, 1024, 16, 3840, 8, 3840, 1, 661, 3, (C + 3839) / 3840, 16.0 * C};
-    printf("%-38s %-8s %10s %8s %8s\n", "shape", "row", "ms/launch", "GB/s", "of 8 TB/s");
+    printf("%-38s %-10s %10s %8s %8s\n", "shape", "row", "ms/launch", "GB/s", "of 8 TB/s");
     auto row = [&](const Shape &s, const char *what, double ms) {
-        printf("%-38s %-8s %10.4f %8.0f %8.4f\n", s.name, what, ms, s.alg_bytes / ms / 1e6, s.alg_bytes / ms / 1e6 / 8000.0);
+        printf("%-38s %-10s %10.4f %8.0f %8.4f\n", s.name, what, ms, s.alg_bytes / ms / 1e6, s.alg_bytes / ms / 1e6 / 8000.0);
         fflush(stdout);
     };
     const char *names[3] = {"mem", "dose", "dose+x"};
@@ -190,6 +310,35 @@ int main(int argc, char **argv)
                                          : (occ == 3 ? run<3, 4>(t, 2, in, C / 4 + 4096, out, seconds, 1e-3f) : run<4, 4>(t, 2, in, C / 4 + 4096, out, seconds, 1e-3f));
                 row(t, what, ms);
             }
+        return 0;
+    }
+    if (argc > 2 && std::string(argv[2]) == "wide") {
+        // tools/floor_lab <seconds> wide [rounds]: the headline's shape, 8-byte rows against 16-byte rows, the rows interleaved round by round
+        const int rounds = argc > 3 ? atoi(argv[3]) : 4;
+        pcx::SchedState *sched;
+        CK(hipMalloc(&sched, 4096));
+        CK(hipMemset(sched, 0, 4096));
+        Shape t = fr;
+        t.nblocks = C / 3840;            // full blocks only: every window inside the buffer, every output row whole
+        t.alg_bytes = 16.0 * 3840 * t.nblocks;
+        t.name = "fir255 dealt";
+        for (int r = 0; r < rounds; r++) {
+            row(t, "mem", run<4, 16>(t, 0, in, C + 4096, out, seconds, 1e-3f));           // the grid-stride row of the table above
+#define DEALT_ROW(NAME, WIDE, NOV, MODE, SWAP) row(t, NAME, run_dealt<WIDE, NOV, MODE, SWAP>(t, in, C + 4096, out, seconds, 1e-3f, sched))
+            DEALT_ROW("mem8 n1", false, 1, 0, false);            // the product's accesses
+            DEALT_ROW("mem8 n2", false, 2, 0, false);
+            DEALT_ROW("mem16 n2", true, 2, 0, false);            // 16-byte rows, the same policy per row pair
+            DEALT_ROW("mem16s n2", true, 2, 0, true);
+            DEALT_ROW("mem8 n4", false, 4, 0, false);
+            DEALT_ROW("mem16 n4", true, 4, 0, false);
+            DEALT_ROW("mem8 n8", false, 8, 0, false);
+            DEALT_ROW("mem16 n8", true, 8, 0, false);
+            DEALT_ROW("dose8 n1", false, 1, 1, false);
+            DEALT_ROW("dose8 n2", false, 2, 1, false);
+            DEALT_ROW("dose16s n2", true, 2, 1, true);
+            DEALT_ROW("dose8 n4", false, 4, 1, false);
+#undef DEALT_ROW
+        }
         return 0;
     }
     for (int m = 0; m < 3; m++) row(fr, names[m], run<4, 16>(fr, m, in, C + 4096, out, seconds, 1e-3f));
