@@ -872,6 +872,25 @@ PCX_API int pcx_mathfn(int scalar, int fn, const void *in, void *out, size_t n);
 PCX_API int pcx_mathfn_dev(int scalar, int fn, const void *in_dev, void *out_dev, size_t n, void *stream);
 PCX_API int pcx_mathfn_param(int scalar, int fn, const void *param, const void *in, void *out, size_t n);
 PCX_API int pcx_mathfn_param_dev(int scalar, int fn, const void *param, const void *in_dev, void *out_dev, size_t n, void *stream);
+/* ---- the special-function blocks (specfn.hip): /comms/gamma, /comms/lngamma, /comms/erf, /comms/erfc, /comms/beta, /comms/modf
+ * (math/Gamma.cpp, ErrorFunction.cpp, Beta.cpp, ModF.cpp; the scalar loops).  PCX_F64 and PCX_F32 only; any other type is
+ * PCX_ERR_ARG ("unsupported type").  pcx_specfn: std::tgamma, std::lgamma, std::erf, std::erfc of every element.  pcx_beta:
+ * exp(lgamma(a) + lgamma(b) - lgamma(a + b)), which is what std::beta computes: a NaN for a NaN, and |B(a, b)| where an argument is
+ * negative.  The value is that expression's: from a larger argument of 1024 on, where lgamma(a) and lgamma(a + b) are huge and cancel,
+ * their difference is taken from Stirling's series.  pcx_modf: out_frac[i] = std::modf(in[i], &out_int[i]); both parts carry the sign of the input, exactly.
+ * Accuracy: as the pcx_mathfn family -- float64 is the device library's function, float32 the same double expression rounded once;
+ * special inputs (poles, infinities, signed zeros) give what C prescribes.
+ * Aliasing: pcx_specfn's `out` may be exactly `in`; pcx_beta's `out` may be exactly in0 or exactly in1, and the inputs may overlap
+ * each other in any way; either output of pcx_modf may be exactly `in`, and the two outputs share no byte.  Any other overlap of an
+ * output is PCX_ERR_ARG.  Buffers may start at any element-aligned byte address.  n == 0 is PCX_OK whatever the pointers.  Every
+ * refusal returns before a device is touched. */
+typedef enum pcx_spec_fn { PCX_SPEC_GAMMA = 0, PCX_SPEC_LNGAMMA = 1, PCX_SPEC_ERF = 2, PCX_SPEC_ERFC = 3 } pcx_spec_fn;
+PCX_API int pcx_specfn(int scalar, int fn, const void *in, void *out, size_t n);
+PCX_API int pcx_specfn_dev(int scalar, int fn, const void *in_dev, void *out_dev, size_t n, void *stream);
+PCX_API int pcx_beta(int scalar, const void *in0, const void *in1, void *out, size_t n);
+PCX_API int pcx_beta_dev(int scalar, const void *in0_dev, const void *in1_dev, void *out_dev, size_t n, void *stream);
+PCX_API int pcx_modf(int scalar, const void *in, void *out_int, void *out_frac, size_t n);
+PCX_API int pcx_modf_dev(int scalar, const void *in_dev, void *out_int_dev, void *out_frac_dev, size_t n, void *stream);
 /* /comms/split_complex, /comms/combine_complex: utility/SplitComplex.cpp:10-18, utility/CombineComplex.cpp:10-17;
  * scalar = the real type of the planes (f64, f32, int64..int8: splitComplexFactory :60-70) */
 PCX_API int pcx_split_complex(int scalar, const void *in, void *re, void *im, size_t n);

@@ -23,6 +23,8 @@ MATH_TRIG_OPS = ("COS", "SIN", "TAN", "SEC", "CSC", "COT", "ACOS", "ASIN", "ATAN
 MATH_FN.update(zip(MATH_TRIG_OPS, range(16, 40)))
 MATH_FN.update(zip(("EXPN", "LOGN", "POW", "NTH_ROOT"), range(48, 52)))
 MATH_FN_PARAM = ("EXPN", "LOGN", "POW", "NTH_ROOT")
+# pcx_spec_fn: name -> code (pcx_specfn); beta and modf have calls of their own
+SPEC_FN = dict(zip(("GAMMA", "LNGAMMA", "ERF", "ERFC"), range(4)))
 # pcx_status
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4
 # pcx_fir_algo
@@ -304,6 +306,12 @@ SIGNATURES = {
     "pcx_mathfn_dev": (_i, [_i, _i, _vp, _vp, _sz, _vp]),
     "pcx_mathfn_param": (_i, [_i, _i, _vp, _vp, _vp, _sz]),
     "pcx_mathfn_param_dev": (_i, [_i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "pcx_specfn": (_i, [_i, _i, _vp, _vp, _sz]),
+    "pcx_specfn_dev": (_i, [_i, _i, _vp, _vp, _sz, _vp]),
+    "pcx_beta": (_i, [_i, _vp, _vp, _vp, _sz]),
+    "pcx_beta_dev": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
+    "pcx_modf": (_i, [_i, _vp, _vp, _vp, _sz]),
+    "pcx_modf_dev": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
     "pcx_split_complex": (_i, [_i, _vp, _vp, _vp, _sz]),
     "pcx_split_complex_dev": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
     "pcx_combine_complex": (_i, [_i, _vp, _vp, _vp, _sz]),

@@ -63,14 +63,15 @@ _blib = None
 # (framer_blocks.cpp: /comms/preamble_framer, /comms/frame_insert), "logic" libpcx_logic_blocks.so (logic_blocks.cpp: /comms/comparator,
 # /comms/const_comparator, /comms/const_arithmetic, /comms/bitwise_unary, /comms/bitwise_binary, /comms/const_bitwise_binary,
 # /comms/bitshift, /comms/byte_order), "math" libpcx_math_blocks.so (math_blocks.cpp: /comms/exp, exp2, exp10, expm1, expN, log, log2, log10,
-# log1p, logN, pow, sqrt, cbrt, nth_root, rsqrt, sinc, sigmoid, trigonometric) -- one registry each, as Pothos loads one module library per source directory
+# log1p, logN, pow, sqrt, cbrt, nth_root, rsqrt, sinc, sigmoid, trigonometric), "special" libpcx_special_blocks.so (special_blocks.cpp:
+# /comms/gamma, lngamma, erf, erfc, beta, modf) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
            "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so"),
            "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so"),
            "framer": os.path.join(_HERE, "libpcx_framer_blocks.so"), "logic": os.path.join(_HERE, "libpcx_logic_blocks.so"),
-           "math": os.path.join(_HERE, "libpcx_math_blocks.so")}
+           "math": os.path.join(_HERE, "libpcx_math_blocks.so"), "special": os.path.join(_HERE, "libpcx_special_blocks.so")}
 _mlibs = {}
 
 

@@ -1000,3 +1000,105 @@ int pcx_mathfn_param(int scalar, int fn, const void *param, const void *in, void
     PCX_TRY(mathfn_args(scalar, fn, true, param, &p));
     return mathfn_host(scalar, fn, p, in, out, n);
 }
+
+/* ---- gamma, lngamma, erf, erfc, beta, modf (specfn.hip) ---- */
+static int specfn_args(int scalar, int fn)
+{
+    PCX_CHECK_ARG(is_float_scalar(scalar), "special function: unsupported type (scalar %d): float32 and float64 only", scalar);
+    PCX_CHECK_ARG(fn >= PCX_SPEC_GAMMA && fn <= PCX_SPEC_ERFC, "special function: unknown function %d", fn);
+    return PCX_OK;
+}
+int pcx_specfn_dev(int scalar, int fn, const void *in_dev, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_TRY(specfn_args(scalar, fn));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in_dev && out_dev, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in_dev, b, out_dev, b, "special function");
+    return launch_specfn(scalar, fn, in_dev, out_dev, n, as_stream(stream));
+}
+int pcx_specfn(int scalar, int fn, const void *in, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_TRY(specfn_args(scalar, fn));
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in, b, out, b, "special function");
+    return run_host_map(in, out, b, b, [&](const void *di, void *dout, hipStream_t st) { return launch_specfn(scalar, fn, di, dout, n, st); });
+}
+int pcx_beta_dev(int scalar, const void *in0_dev, const void *in1_dev, void *out_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(is_float_scalar(scalar), "beta: unsupported type (scalar %d): float32 and float64 only", scalar);
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in0_dev && in1_dev && out_dev, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in0_dev, b, out_dev, b, "beta");
+    PCX_CHECK_OVERLAP(in1_dev, b, out_dev, b, "beta");
+    return launch_beta(scalar, in0_dev, in1_dev, out_dev, n, as_stream(stream));
+}
+int pcx_beta(int scalar, const void *in0, const void *in1, void *out, size_t n)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(is_float_scalar(scalar), "beta: unsupported type (scalar %d): float32 and float64 only", scalar);
+    if (n == 0) return PCX_OK;
+    PCX_CHECK_ARG(in0 && in1 && out, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in0, b, out, b, "beta");
+    PCX_CHECK_OVERLAP(in1, b, out, b, "beta");
+    MapWs *ws;
+    PCX_TRY(map_ws(&ws));
+    const void *d0, *d1; void *dout; bool staged;
+    PCX_TRY(stage_reserve(in1, b, ws->in2));
+    PCX_TRY(stage_reserve(out, b, ws->out));
+    PCX_TRY(stage_in(in0, b, ws->in, ws->st, &d0));
+    PCX_TRY(stage_in(in1, b, ws->in2, ws->st, &d1));
+    PCX_TRY(stage_out_begin(out, b, ws->out, &dout, &staged));
+    {
+        LinkBound shape(in0, in1, out);
+        PCX_TRY(launch_beta(scalar, d0, d1, dout, n, ws->st));
+    }
+    return stage_out_end(out, b, ws->out, staged, ws->st);
+}
+// modf's buffers: either output may be exactly `in`, the outputs share no byte, any other overlap is refused
+static int modf_args(int scalar, const void *in, void *out_int, void *out_frac, size_t n)
+{
+    PCX_CHECK_ARG(in && out_int && out_frac, "null buffer");
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    PCX_CHECK_OVERLAP(in, b, out_int, b, "modf");
+    PCX_CHECK_OVERLAP(in, b, out_frac, b, "modf");
+    PCX_CHECK_ARG(map_overlap_ok(out_int, b, out_frac, b, false), "modf: one output overlaps the other");
+    return PCX_OK;
+}
+int pcx_modf_dev(int scalar, const void *in_dev, void *out_int_dev, void *out_frac_dev, size_t n, void *stream)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(is_float_scalar(scalar), "modf: unsupported type (scalar %d): float32 and float64 only", scalar);
+    if (n == 0) return PCX_OK;
+    PCX_TRY(modf_args(scalar, in_dev, out_int_dev, out_frac_dev, n));
+    return launch_modf(scalar, in_dev, out_int_dev, out_frac_dev, n, as_stream(stream));
+}
+int pcx_modf(int scalar, const void *in, void *out_int, void *out_frac, size_t n)
+{
+    PCX_TRACE();
+    PCX_CHECK_ARG(is_float_scalar(scalar), "modf: unsupported type (scalar %d): float32 and float64 only", scalar);
+    if (n == 0) return PCX_OK;
+    PCX_TRY(modf_args(scalar, in, out_int, out_frac, n));
+    const size_t b = n * (size_t)scalar_bytes(scalar);
+    MapWs *ws;
+    PCX_TRY(map_ws(&ws));
+    const void *din; void *dint, *dfrac; bool sint, sfrac;
+    PCX_TRY(stage_reserve(out_int, b, ws->out));
+    PCX_TRY(stage_reserve(out_frac, b, ws->out2));
+    PCX_TRY(stage_in(in, b, ws->in, ws->st, &din));
+    PCX_TRY(stage_out_begin(out_int, b, ws->out, &dint, &sint));
+    PCX_TRY(stage_out_begin(out_frac, b, ws->out2, &dfrac, &sfrac));
+    {
+        LinkBound shape(in, out_int, out_frac);
+        PCX_TRY(launch_modf(scalar, din, dint, dfrac, n, ws->st));
+    }
+    PCX_TRY(stage_out_end(out_int, b, ws->out, sint, ws->st));
+    return stage_out_end(out_frac, b, ws->out2, sfrac, ws->st);
+}

@@ -230,6 +230,10 @@ int launch_byteswap(int width, const void *in, void *out, size_t n_scalars, hipS
 int launch_arith_const(int scalar, int is_complex, int op, const void *in, const void *k, void *out, size_t n, hipStream_t st);
 // (mathfn.hip) one function of pcx_math_fn over n float32 / float64 elements; `param` is the parameter of the codes from PCX_MATH_EXPN on
 int launch_mathfn(int scalar, int fn, double param, const void *in, void *out, size_t n, hipStream_t st);
+// (specfn.hip) one function of pcx_spec_fn, the beta function of two streams, and modf's two parts, over n float32 / float64 elements
+int launch_specfn(int scalar, int fn, const void *in, void *out, size_t n, hipStream_t st);
+int launch_beta(int scalar, const void *in0, const void *in1, void *out, size_t n, hipStream_t st);
+int launch_modf(int scalar, const void *in, void *out_int, void *out_frac, size_t n, hipStream_t st);
 // (dc_removal.hip) /comms/dc_removal: the shape of a configured handle and its two paths
 struct DcrShape {
     int scalar = PCX_F32;

@@ -1486,6 +1486,73 @@ def math_fn(name, x, param=None, out=None, stream=None):
     return out
 
 
+def _float_operands(*xs):
+    """(scalar, element count) of operands that must agree in kind, type and size; a type the calls refuse maps to I8"""
+    x = xs[0]
+    if _is_torch(x):
+        import torch
+        if any(not _is_torch(a) or a.dtype != x.dtype or a.numel() != x.numel() for a in xs):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "operands must be device tensors of one type and size")
+        return {torch.float64: F64, torch.float32: F32}.get(x.dtype, I8), x.numel()
+    if any(_is_torch(a) or a.dtype != x.dtype or a.size != x.size for a in xs):
+        raise _lib.InvalidArgument(_lib.ERR_ARG, "operands must be arrays of one type and size")
+    return SCALAR_OF_NP.get(x.dtype, I8), x.size
+
+
+def special_fn(name, x, out=None, stream=None):
+    """out[i] = f(x[i]) for one function of pcx_spec_fn, by name: "GAMMA", "LNGAMMA", "ERF", "ERFC"; float32 and float64.  A numpy
+    array goes the host path, a device tensor stays on the device (`out` may be x itself; a new tensor by default)."""
+    L = _lib.load()
+    code = _op_code(_lib.SPEC_FN, str(name).upper(), "special function")
+    if _is_torch(x):
+        import torch
+        out = torch.empty_like(x) if out is None else out
+        scalar, n = _float_operands(x, out)
+        _lib.check(L.pcx_specfn_dev(scalar, code, _dev_ptr(x), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    x = np.ascontiguousarray(x)
+    out = np.zeros_like(x) if out is None else out
+    scalar, n = _float_operands(x, out)
+    _lib.check(L.pcx_specfn(scalar, code, _np_ptr(x), _np_ptr(out), n))
+    return out
+
+
+def beta(a, b, out=None, stream=None):
+    """out[i] = exp(lgamma(a[i]) + lgamma(b[i]) - lgamma(a[i] + b[i])), the beta function as std::beta computes it (its magnitude where
+    an argument is negative); float32 and float64, a and b of one type and size.  `out` may be a or b itself."""
+    L = _lib.load()
+    if _is_torch(a):
+        import torch
+        out = torch.empty_like(a) if out is None else out
+        scalar, n = _float_operands(a, b, out)
+        _lib.check(L.pcx_beta_dev(scalar, _dev_ptr(a), _dev_ptr(b), _dev_ptr(out), n, _stream_ptr(stream)))
+        return out
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    out = np.zeros_like(a) if out is None else out
+    scalar, n = _float_operands(a, b, out)
+    _lib.check(L.pcx_beta(scalar, _np_ptr(a), _np_ptr(b), _np_ptr(out), n))
+    return out
+
+
+def modf(x, out_int=None, out_frac=None, stream=None):
+    """(int, frac) with frac[i] = std::modf(x[i], &int[i]): the integral and the fractional part, both with the sign of x[i]; float32
+    and float64.  Either output may be x itself; the two outputs share nothing."""
+    L = _lib.load()
+    if _is_torch(x):
+        import torch
+        out_int = torch.empty_like(x) if out_int is None else out_int
+        out_frac = torch.empty_like(x) if out_frac is None else out_frac
+        scalar, n = _float_operands(x, out_int, out_frac)
+        _lib.check(L.pcx_modf_dev(scalar, _dev_ptr(x), _dev_ptr(out_int), _dev_ptr(out_frac), n, _stream_ptr(stream)))
+        return out_int, out_frac
+    x = np.ascontiguousarray(x)
+    out_int = np.zeros_like(x) if out_int is None else out_int
+    out_frac = np.zeros_like(x) if out_frac is None else out_frac
+    scalar, n = _float_operands(x, out_int, out_frac)
+    _lib.check(L.pcx_modf(scalar, _np_ptr(x), _np_ptr(out_int), _np_ptr(out_frac), n))
+    return out_int, out_frac
+
+
 def byteswap(x, width=None, out=None, n=None, stream=None):
     """every scalar of `width` = 2, 4 or 8 bytes reversed (digital/ByteOrder.hpp); n counts scalars, a complex element is two"""
     L = _lib.load()
