@@ -35,7 +35,9 @@ namespace pcx {
 // range check, which drops both the K-1 aliased samples and anything past n_out.
 // PREFETCH: keep the next block's 16 samples per lane in flight in registers (168 VGPRs, 3
 // workgroups per CU) or load at the top of each block (128 VGPRs, 4 workgroups per CU).
-// LAUX / SAUX: cache-policy bits of the stream loads / stores (LAUX >= 4: per-row policy, see fetch).
+// LROWS / SROWS: the rows of the window / of the block's outputs that are loaded / stored on the DEFAULT cache policy, one bit per
+// row (ols_block.hpp); the other rows are loaded non-temporal and stored with the policy bits SAUX (2 = nt; sc0 = 1, sc1 = 16 in the
+// diag variants).  kRowsAll = plain accesses, kRowsNone = every access nt, rows_ends(n) = n plain rows at either end of the window.
 // Measured at K = 255, one box, 64 Mi samples: plain 0.2269-0.2280 ms; nt on every load 0.2311 with
 // nt stores (consecutive blocks re-read the overlap, and those hits are lost when the first touch
 // bypasses L2); nt stores alone 0.2267-0.2277; nt stores + nt loads on the rows that only this block
@@ -47,7 +49,7 @@ namespace pcx {
 // -- room for the register prefetch at 4 workgroups per CU.
 // XCH: 1 = the transform pair with its second exchange inside sixteen lanes (fft4096.hpp: three barriers per block), 0 = the
 // Stockham passes both ways (eight)
-template <bool PREFETCH, int LAUX = 0, int SAUX = 0, int CHUNKED = 0, int DIAG = 0, bool HGLOBAL = false, bool GATED = false, int XCH = 0>
+template <bool PREFETCH, unsigned LROWS = fft4k::kRowsAll, unsigned SROWS = fft4k::kRowsAll, int SAUX = 2, int CHUNKED = 0, int DIAG = 0, bool HGLOBAL = false, bool GATED = false, int XCH = 0>
 __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_ols4096_kernel(const float2 *__restrict__ in, size_t in_elems,
                                                                   float2 *__restrict__ out, size_t n_out,
                                                                   const float2 *__restrict__ Hspec, int Kov, int pad,
@@ -99,21 +101,9 @@ __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_
     auto fetch = [&](cf (&dst)[16], size_t blk) {
         if (DIAG == 1) blk = first_full;
         if (blk >= first_full && blk < nfull) {
-            if (LAUX >= 4) {
-                // NOV = 1 << (LAUX-4) rows at either end of the window hold the (aligned) overlap with
-                // the neighbouring blocks: cached normally so the second reader hits in L2.  The rows
-                // between are touched by this block only: non-temporal.
-                constexpr int NOV = 1 << (LAUX >= 4 ? LAUX - 4 : 0);
-                const __amdgpu_buffer_rsrc_t rs = make_rsrc(in + blk * S - pad, N * 8);
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const u32x2 t = (r < NOV || r >= 16 - NOV) ? __builtin_amdgcn_raw_buffer_load_b64(rs, j * 8, 2048 * r, 0)
-                                                               : __builtin_amdgcn_raw_buffer_load_b64(rs, j * 8, 2048 * r, 2);
-                    dst[r] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
-                }
-            } else {
-                load_frame<false, LAUX>(dst, make_rsrc(in + blk * S - pad, N * 8), j);
-            }
+            // the rows at either end of the window hold the (aligned) overlap with the neighbouring blocks: in LROWS, cached normally,
+            // so that the second reader hits in L2.  The rows outside LROWS are non-temporal.
+            load_window_rows<LROWS, false>(dst, make_rsrc(in + blk * S - pad, N * 8), j);
         } else {
             // ragged: block 0 when pad > 0 (its window would start before the buffer: those samples
             // only feed dropped outputs, read as 0 through the range check) and the tail block
@@ -124,7 +114,7 @@ __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_
             const __amdgpu_buffer_rsrc_t rs = make_rsrc(in + first, (unsigned)((left < want ? left : want) * 8));
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rs, (j + 256 * r - (int)shift) * 8, 0, LAUX >= 4 ? 0 : LAUX);
+                const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(rs, (j + 256 * r - (int)shift) * 8, 0, LROWS == kRowsNone ? 2 : 0);
                 dst[r] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
             }
         }
@@ -211,7 +201,7 @@ __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_
         for (int q = 0; q < 16; q++) {
             const int row = 256 * bin_of(q);
             if (row + 255 < Kov) continue;                    // whole row dropped: uniform skip
-            store_cf<SAUX>(ws, vbase + (unsigned)row * 8u, DIAG == 2 ? cf{u[q].x, -u[q].y} : u[q]);
+            store_row_cf<SROWS, SAUX>(ws, vbase + (unsigned)row * 8u, DIAG == 2 ? cf{u[q].x, -u[q].y} : u[q], bin_of(q));
         }
         __builtin_amdgcn_s_setprio(0);
         if (CHUNKED == 3) {
@@ -252,9 +242,9 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
     const int variant = (int)PCX_ENV_INT("PCX_OLS_VARIANT", -1);
     const int align = (int)PCX_ENV_INT("PCX_OLS_ALIGN", 1);
 #ifdef PCX_DIAG
-    const bool one_near_row = PCX_ENV_INT("PCX_OLS_NEAR_ROWS", 2) == 1;     // the default policy with ONE normally cached row at either end of the window (below)
+    const long near_rows = PCX_ENV_INT("PCX_OLS_NEAR_ROWS", 0);     // 1 / 2: ONE / TWO normally cached rows at either end of the window in place of the default mix (below)
 #else
-    constexpr bool one_near_row = false;
+    constexpr long near_rows = 0;
 #endif
 #ifdef PCX_DIAG
     if (variant == 10 || variant == 11 || variant == 12 || variant == 13 || variant == 15 || variant == 16) {
@@ -282,74 +272,81 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
     // the window of block b starts at sample b*S - pad: only block 0 reaches below K-1 (Kov <= 2048 <= S)
     const Gate gate{dealt ? (const unsigned *)gate_word : nullptr, gate_value, 1u};
     if (gated && gate.word) *gated = 1;
+    // the dealt launches' grid: 4 resident workgroups per CU, all of them drawing.
+    // (Leaving a few of the 1024 resident slots empty in the gated launch, so that the kernels the gate waits for -- the halo's receive or
+    // copy, the one-thread signal -- find room beside this launch, measured no better: 0.2196 ms at 1024 workgroups, 0.2242 at 1008,
+    // two shards on one device, profiles/r03/shard_probe.txt.  PCX_GATED_SLOTS / PCX_DEALT_SLOTS (diag) set the number.)
+    const long env_gated = PCX_ENV_INT("PCX_GATED_SLOTS", 0), env_dealt = PCX_ENV_INT("PCX_DEALT_SLOTS", 0);
+    const long env_gd = gate.word ? env_gated : env_dealt;
+    const unsigned gd = env_gd > 0 ? (unsigned)env_gd : slots;
+    // row masks of the instantiations below (ols_block.hpp): every mask given to an overlap Kov keeps the ceil(Kov / 256) rows at either
+    // end of the window, which the neighbouring blocks read too, on the default policy
+    constexpr unsigned ALL = fft4k::kRowsAll, NONE = fft4k::kRowsNone, E1 = fft4k::rows_ends(1), E2 = fft4k::rows_ends(2), E4 = fft4k::rows_ends(4);
+    constexpr unsigned MIX = 0xAA55u;      // rows 0 2 4 6 9 11 13 15
+    static_assert(fft4k::rows_shared_kept(E1) == 1 && fft4k::rows_shared_kept(E2) == 2 && fft4k::rows_shared_kept(E4) == 4 && fft4k::rows_shared_kept(ALL) == 8 && fft4k::rows_shared_kept(MIX) == 1, "the Kov ladder below");
 #define PCX_OLS_LAUNCH(KERN, GRID) hipLaunchKernelGGL(KERN, dim3(GRID), dim3(256), 0, st, pi, in_elems, po, n_out, ph, (int)Kov, (int)pad, pt, first_full, nfull, nblocks, (SchedState *)sched, gate)
 #ifdef PCX_DIAG
     switch (variant) {
     case 0: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<true>), g3); goto launched;
     case 1: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false>), g4); goto launched;
-    case 2: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 2, 0>), g4); goto launched;
-    case 3: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 2, 2>), g4); goto launched;
-    case 4: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 0, 1>), g4); goto launched;
-    case 5: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<true, 0, 0, 0, 0, true>), g4); goto launched;
-    case 6: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2>), g4); goto launched;
-    case 7: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 0>), g4); goto launched;
-    case 9: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<true, 4, 2>), g3); goto launched;
-    case 14: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 2>), gx); goto launched;
+    case 2: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, NONE, ALL>), g4); goto launched;
+    case 3: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, NONE, NONE, 2>), g4); goto launched;
+    case 4: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, ALL, ALL, 2, 1>), g4); goto launched;
+    case 5: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<true, ALL, ALL, 2, 0, 0, true>), g4); goto launched;
+    case 6: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, ALL, NONE, 2>), g4); goto launched;
+    case 7: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, ALL>), g4); goto launched;
+    case 9: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<true, E1, NONE, 2>), g3); goto launched;
+    case 14: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 2>), gx); goto launched;
     // 20 / 21: static stride on a grid of PCX_ROUNDS blocks per workgroup (default 3), H held in registers / fetched from L2 per block
-    case 20: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2>), rounds_grid(nblocks, 1024, 3)); goto launched;
-    case 21: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 0, true>), rounds_grid(nblocks, 1024, 3)); goto launched;
-    case 15: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 3>), g4); goto launched;
-    case 16: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 4>), g4); goto launched;
-    case 12: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 1>), g4); goto launched;
-    case 13: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 2>), g4); goto launched;
-    // 30..34: the product kernel with other cache-policy bits on its stores (sc0 = 1, nt = 2, sc1 = 16)
-    case 30: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 0, 3, 0, false, false, 1>), g4); goto launched;
-    case 31: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 3, 3, 0, false, false, 1>), g4); goto launched;
-    case 32: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 18, 3, 0, false, false, 1>), g4); goto launched;
-    case 33: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 19, 3, 0, false, false, 1>), g4); goto launched;
-    case 34: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 16, 3, 0, false, false, 1>), g4); goto launched;
-    case 35: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 17, 3, 0, false, false, 1>), g4); goto launched;
-    case 10: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 0, 0, 1>), g4); goto launched;
-    case 11: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 0, 0, 2>), g4); goto launched;
+    case 20: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2>), rounds_grid(nblocks, 1024, 3)); goto launched;
+    case 21: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 0, 0, true>), rounds_grid(nblocks, 1024, 3)); goto launched;
+    case 15: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 0, 3>), g4); goto launched;
+    case 16: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 0, 4>), g4); goto launched;
+    case 12: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 0, 1>), g4); goto launched;
+    case 13: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 0, 2>), g4); goto launched;
+    // 30..35: the round-6 product kernel with other cache-policy bits on ALL its stores (30: default; sc0 = 1, nt = 2, sc1 = 16)
+    case 30: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, ALL, 2, 3, 0, false, false, 1>), g4); goto launched;
+    case 31: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 3, 3, 0, false, false, 1>), g4); goto launched;
+    case 32: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 18, 3, 0, false, false, 1>), g4); goto launched;
+    case 33: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 19, 3, 0, false, false, 1>), g4); goto launched;
+    case 34: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 16, 3, 0, false, false, 1>), g4); goto launched;
+    case 35: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 17, 3, 0, false, false, 1>), g4); goto launched;
+    case 10: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, ALL, ALL, 2, 0, 1>), g4); goto launched;
+    case 11: PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, ALL, ALL, 2, 0, 2>), g4); goto launched;
     default: break;
     }
 #else
     (void)variant; (void)g3; (void)gx;
 #endif
-    // non-temporal stores; non-temporal loads for the rows in the middle of the window; blocks dealt dynamically when the caller
+    // non-temporal stores; non-temporal loads for the rows outside the policy's mask; blocks dealt dynamically when the caller
     // brought the counter pair (every pcx_fir handle does), else the grid stride.
-    // Up to Kov = 256 only rows 0 and 15 are shared with a neighbouring block, yet TWO rows at either end are cached normally
-    // (LAUX 5, the kernels of Kov <= 512): on the loads and stores alone of this launch shape that measured 0.1676 ms against
-    // 0.1764 with one row at either end (tools/floor_lab.hip `wide`, profiles/r07/floor_wide_rows.txt).
-    // PCX_OLS_NEAR_ROWS=1 (diag) brings the one-row policy back, for A/B
-    if (dealt && gate.word) {
-        // (Leaving a few of the 1024 resident slots empty, so that the kernels the gate waits for -- the halo's receive or copy, the
-        // one-thread signal -- find room beside this launch, measured no better: 0.2196 ms at 1024 workgroups, 0.2242 at 1008,
-        // two shards on one device, profiles/r03/shard_probe.txt.  PCX_GATED_SLOTS (diag) sets the number.)
-        const long env_gd = PCX_ENV_INT("PCX_GATED_SLOTS", 0);
-        const unsigned gd = env_gd > 0 ? (unsigned)env_gd : slots;
-        if (Kov <= 256 && one_near_row) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 3, 0, false, true, 1>), gd);
-        else if (Kov <= 512) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 5, 2, 3, 0, false, true, 1>), gd);
-        else if (Kov <= 1024) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 6, 2, 3, 0, false, true, 1>), gd);
-        else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 3, 0, false, true, 1>), gd);
-    } else if (dealt) {
-        const long env_gd = PCX_ENV_INT("PCX_DEALT_SLOTS", 0);
-        const unsigned gd = env_gd > 0 ? (unsigned)env_gd : slots;   // 4 resident workgroups per CU, all of them drawing
+    // Up to Kov = 256 only rows 0 and 15 are shared with a neighbouring block, yet EIGHT of the sixteen rows are cached normally: every
+    // other row, 0 2 4 6 9 11 13 15 (MIX).  What counts is HOW MANY rows take each policy, not which: on the loads and stores alone of
+    // this launch shape one row at either end measured 0.1764 ms, two 0.1676, three 0.1605, four 0.1593, five 0.1678, every row 0.1845,
+    // and eight rows as every other row or as 2 + 6 0.1575 (tools/floor_lab.hip `rows`, profiles/r08/floor_row_policy.txt).  HBM and
+    // L2 traffic are the same for all of them; what falls and rises with the time is the stall counters of L1 and L2.
+    // Product A/B, 255 taps: 0.1828-0.1829 ms against the two-row policy's 0.1861-0.1862 (profiles/r08/ab_row_policy.txt).
+    // MIX keeps ONE row at either end: it serves Kov <= 256, the larger overlaps keep the kernels they had.
+    // PCX_OLS_NEAR_ROWS=1 / 2 (diag) bring the one-row / two-row policies of the rounds before back, for A/B
+    // One policy = three instantiations: the gated dealt, the dealt and the grid-stride kernel.
+#define PCX_OLS_POLICY(LROWS)                                                                                                       \
+    do {                                                                                                                            \
+        if (dealt && gate.word) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 3, 0, false, true, 1>), gd);         \
+        else if (dealt) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 3, 0, false, false, 1>), gd);                \
+        else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 0, 0, false, false, 1>), g4);                           \
+    } while (0)
 #ifdef PCX_DIAG
-        if (PCX_ENV_INT("PCX_OLS_XCH", 1) == 0) {       // the eight-barrier Stockham pair, for A/B
-            if (Kov <= 256) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 3>), gd);
-            else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 3>), gd);
-        } else
+    if (dealt && !gate.word && PCX_ENV_INT("PCX_OLS_XCH", 1) == 0) {       // the eight-barrier Stockham pair, for A/B
+        if (Kov <= 256) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 3>), gd);
+        else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, ALL, NONE, 2, 3>), gd);
+    } else if (Kov <= 256 && near_rows == 1) PCX_OLS_POLICY(E1);
+    else
 #endif
-        if (Kov <= 256 && one_near_row) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 3, 0, false, false, 1>), gd);
-        else if (Kov <= 512) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 5, 2, 3, 0, false, false, 1>), gd);
-        else if (Kov <= 1024) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 6, 2, 3, 0, false, false, 1>), gd);
-        else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 3, 0, false, false, 1>), gd);
-    }
-    else if (Kov <= 256 && one_near_row) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 4, 2, 0, 0, false, false, 1>), g4);
-    else if (Kov <= 512) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 5, 2, 0, 0, false, false, 1>), g4);
-    else if (Kov <= 1024) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 6, 2, 0, 0, false, false, 1>), g4);
-    else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, 0, 2, 0, 0, false, false, 1>), g4);
+    if (Kov <= 256 * (size_t)fft4k::rows_shared_kept(MIX) && near_rows != 2) PCX_OLS_POLICY(MIX);
+    else if (Kov <= 512) PCX_OLS_POLICY(E2);
+    else if (Kov <= 1024) PCX_OLS_POLICY(E4);
+    else PCX_OLS_POLICY(ALL);
+#undef PCX_OLS_POLICY
 #ifdef PCX_DIAG
 launched:
 #endif
@@ -611,7 +608,7 @@ int launch_interleave_rows_cf32(const void *rows, void *out, size_t n, size_t L,
 // sample (8 in, 4 out).  The overlap is rounded up to a multiple of 32 samples (aligned 1 KiB
 // output rows); 128 VGPRs, 4 workgroups per CU.
 // --------------------------------------------------------------------------------- //
-template <int OCC, int NOV, int SAUX, bool DYN = false, bool GATED = false>
+template <int OCC, int NOV, unsigned LROWS, unsigned SROWS, int SAUX, bool DYN = false, bool GATED = false>
 __global__ __launch_bounds__(256, OCC) void fmchain_cf32_ols4096_kernel(const float2 *__restrict__ in, size_t in_elems,
                                                                         float *__restrict__ out, size_t n_out,
                                                                         const float2 *__restrict__ Hspec, int K, int pad,
@@ -643,17 +640,11 @@ __global__ __launch_bounds__(256, OCC) void fmchain_cf32_ols4096_kernel(const fl
     auto fetch = [&](cf (&dst)[16], size_t blk) {
         const size_t lead = (size_t)(1 + pad);
         if (blk > 0 && blk * S - lead + N <= in_elems) {
-            // as in fir_cf32_ols4096_kernel: the NOV rows at either end are shared with the neighbouring
-            // blocks (cached normally), the rows between are read once (non-temporal)
-            const __amdgpu_buffer_rsrc_t rs = make_rsrc(in + blk * S - lead, N * 8);
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                // row r at byte 2048 r: the odd rows' 2048 goes into the instruction's 12-bit offset field, so eight scalar
-                // offsets serve sixteen rows
-                const u32x2 t = (r < NOV || r >= 16 - NOV) ? __builtin_amdgcn_raw_buffer_load_b64(rs, j * 8 + 2048 * (r & 1), 4096 * (r >> 1), 0)
-                                                           : __builtin_amdgcn_raw_buffer_load_b64(rs, j * 8 + 2048 * (r & 1), 4096 * (r >> 1), 2);
-                dst[r] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
-            }
+            // as in fir_cf32_ols4096_kernel: the rows in LROWS (the NOV at either end, shared with the neighbouring blocks, among them)
+            // are cached normally, the others read non-temporal.  Row r at byte 2048 r: the odd rows' 2048 goes into the instruction's
+            // 12-bit offset field, so eight scalar offsets serve sixteen rows
+            static_assert(rows_shared_kept(LROWS) >= NOV, "every row a neighbouring block reads too stays on the default policy");
+            load_window_rows<LROWS, true>(dst, make_rsrc(in + blk * S - lead, N * 8), j);
             return;
         }
         const int shift = blk == 0 ? 1 + pad : 0;
@@ -773,9 +764,16 @@ __global__ __launch_bounds__(256, OCC) void fmchain_cf32_ols4096_kernel(const fl
             asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(rn) : "s"(KPI), "v"(r));   // pi - r
             r = cf{__float_as_int(x0) < 0 ? rn.x : r.x, __float_as_int(x1) < 0 ? rn.y : r.y};
             const float d0 = __builtin_copysignf(r.x, y0), d1 = __builtin_copysignf(r.y, y1);
+            // (row k of SROWS: the default policy, else the bits SAUX; k is a constant of the unrolled loop, every select here folds)
             auto put = [&](int k, float d) {
-                if (k >= NOV) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), ws, (int)j4, 1024 * k - k4, SAUX);
-                else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), ws, (int)(j4 + (unsigned)(1024 * k - k4)), 0, SAUX);   // = ((j - K) * 4 + 1024 k) mod 2^32
+                const bool plain = (SROWS >> k) & 1u;
+                if (k >= NOV) {
+                    if (plain) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), ws, (int)j4, 1024 * k - k4, 0);
+                    else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), ws, (int)j4, 1024 * k - k4, SAUX);
+                } else {                                                                                               // = ((j - K) * 4 + 1024 k) mod 2^32
+                    if (plain) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), ws, (int)(j4 + (unsigned)(1024 * k - k4)), 0, 0);
+                    else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), ws, (int)(j4 + (unsigned)(1024 * k - k4)), 0, SAUX);
+                }
             };
             put(k0, d0);
             put(k1, d1);
@@ -817,32 +815,45 @@ int launch_fmchain_cf32_ols4096(const void *in, size_t in_elems, void *out, size
     // too when S == Kov (2048 taps)
     const Gate gate{dyn ? (const unsigned *)gate_word : nullptr, gate_value, S < Kov + 1 ? 2u : 1u};
     if (gated && gate.word) *gated = 1;
-#define PCX_FM_LAUNCH(OCC, NOV, SAUX, CAP)                                                                                       \
+#define PCX_FM_LAUNCH(OCC, NOV, LROWS, CAP)                                                                                      \
     do {                                                                                                                         \
         if (dyn && gate.word)                                                                                                    \
-            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, SAUX, true, true>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
+            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2, true, true>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
                                in_elems, (float *)out, n_out, (const float2 *)Hspec, (int)Kov, (int)pad, (const float2 *)tw4096,  \
                                nblocks, (const float2 *)prev_in, (float2 *)prev_out, (SchedState *)sched, gate);                  \
         else if (dyn)                                                                                                            \
-            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, SAUX, true>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
+            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2, true>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
                                in_elems, (float *)out, n_out, (const float2 *)Hspec, (int)Kov, (int)pad, (const float2 *)tw4096,  \
                                nblocks, (const float2 *)prev_in, (float2 *)prev_out, (SchedState *)sched, gate);                  \
         else                                                                                                                     \
-            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, SAUX>), dim3(persistent_grid(nblocks, CAP)), dim3(256), 0, st, \
+            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2>), dim3(persistent_grid(nblocks, CAP)), dim3(256), 0, st, \
                                (const float2 *)in, in_elems, (float *)out, n_out, (const float2 *)Hspec, (int)Kov, (int)pad,      \
                                (const float2 *)tw4096, nblocks, (const float2 *)prev_in, (float2 *)prev_out, (SchedState *)nullptr, gate); \
     } while (0)
 #ifdef PCX_DIAG
-    if (occ == 3) PCX_FM_LAUNCH(3, 8, 0, 768);            // A/B: 3 workgroups per CU, plain loads and stores
-    else if (occ == 5) PCX_FM_LAUNCH(4, 8, 0, 1024);      // A/B: plain loads and stores
+#define SR fft4k::kRowsAll
+    if (occ == 3) PCX_FM_LAUNCH(3, 8, fft4k::kRowsAll, 768);            // A/B: 3 workgroups per CU, plain loads and stores
+    else if (occ == 5) PCX_FM_LAUNCH(4, 8, fft4k::kRowsAll, 1024);      // A/B: plain loads and stores
+#undef SR
     else
 #else
     (void)occ;
 #endif
-    if (Kov <= 256) PCX_FM_LAUNCH(4, 1, 2, slots);
-    else if (Kov <= 512) PCX_FM_LAUNCH(4, 2, 2, slots);
-    else if (Kov <= 1024) PCX_FM_LAUNCH(4, 4, 2, slots);
-    else PCX_FM_LAUNCH(4, 8, 2, slots);
+    // SR: the stored rows on the default policy -- none: every store non-temporal.  The loads beyond Kov = 256: NOV rows at either end on the default policy
+#define SR fft4k::kRowsNone
+    // Up to Kov = 256: every other row of the window on the default policy (0 2 4 6 9 11 13 15), as launch_fir_cf32_ols4096 and for its
+    // reason -- half the rows on either policy is the fastest split of the loads.  Interleaved A/B at 127 taps: 0.1963-0.1965 ms against
+    // 0.1994-0.2000 with one row at either end, 0.1974-0.1981 with two (profiles/r08/ab_row_policy.txt).
+    // PCX_OLS_NEAR_ROWS=1 (diag) brings the one-row policy back, for A/B
+#ifdef PCX_DIAG
+    if (Kov <= 256 && PCX_ENV_INT("PCX_OLS_NEAR_ROWS", 0) == 1) PCX_FM_LAUNCH(4, 1, fft4k::rows_ends(1), slots);
+    else
+#endif
+    if (Kov <= 256) PCX_FM_LAUNCH(4, 1, 0xAA55u, slots);
+    else if (Kov <= 512) PCX_FM_LAUNCH(4, 2, fft4k::rows_ends(2), slots);
+    else if (Kov <= 1024) PCX_FM_LAUNCH(4, 4, fft4k::rows_ends(4), slots);
+    else PCX_FM_LAUNCH(4, 8, fft4k::kRowsAll, slots);
+#undef SR
 #undef PCX_FM_LAUNCH
     PCX_LAUNCH_CHECK();
     return PCX_OK;

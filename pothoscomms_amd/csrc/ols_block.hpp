@@ -6,7 +6,9 @@
 // around a memory access -- the window fetch, the 256-point sub-transforms through LDS, the row stores -- do NOT: taken out of
 // a kernel into a function they come back with another register assignment and another instruction order (what their unrolled
 // loops hold that does not change from block to block -- row tests, row offsets, descriptor bases -- is hoisted to another place
-// in the kernel's prologue), in kernels that are a few registers from spilling.  Those stay written out where they are.
+// in the kernel's prologue), in kernels that are a few registers from spilling.  Those stay written out where they are -- but for the
+// full-block window fetch and the policy select of a row store of the two complex_float32 kernels of fir_ols.hip (below), which
+// compile to the parent's instructions (profiles/r08/resource_usage.txt).
 // The `asm volatile("" : "+v"(..))` / "+s" pins that keep a loop-invariant load inside a kernel's block loop are decisions of
 // that kernel and stay at its call site: these functions take the pinned pointer.
 #pragma once
@@ -14,6 +16,47 @@
 
 namespace pcx {
 namespace fft4k {
+
+// ---- which stream rows take the default cache policy ----
+// A block's window is sixteen 2 KiB rows, row r = samples 256 r .. 256 r + 255, and so is what it stores.  A row mask has bit r set for a
+// row accessed on the DEFAULT cache policy; the other rows are non-temporal.  Consecutive blocks overlap by Kov samples: the
+// ceil(Kov / 256) rows at either end of a window are read by a neighbouring block as well and MUST be in a load mask (their second
+// reader hits in L2: that holds HBM traffic at 1.03 x algorithmic).  What a mask holds beyond them is tuning
+// (tools/floor_lab.hip `rows`).
+constexpr unsigned kRowsAll = 0xFFFFu, kRowsNone = 0u;
+constexpr unsigned rows_ends(int n) { return ((1u << n) - 1u) | (((1u << n) - 1u) << (16 - n)); }     // n rows at either end, n = 1 .. 8
+// the largest n with rows_ends(n) inside the mask: a launcher may give the mask to overlaps Kov <= 256 n, and to no larger one
+constexpr int rows_shared_kept(unsigned mask)
+{
+    int n = 0;
+    while (n < 8 && (rows_ends(n + 1) & ~mask) == 0) n++;
+    return n;
+}
+
+// ---- the window fetch of a full block (the fast path: every row inside the buffer) ----
+// dst[r] = row r of the window behind the descriptor, lane j on column j: sixteen unconditional raw_buffer_load_b64, the policy of each a
+// compile-time bit of DEFAULT_ROWS (the select below folds per row once the loop is unrolled: no branch reaches the ISA).
+// PAIRED = false: the row's displacement 2048 r in the scalar offset (fir_cf32_ols4096_kernel); true: the odd rows' 2048 in the
+// instruction's 12-bit offset field, so that eight scalar offsets serve sixteen rows (fmchain_cf32_ols4096_kernel).
+template <unsigned DEFAULT_ROWS, bool PAIRED>
+__device__ __forceinline__ void load_window_rows(cf (&dst)[16], __amdgpu_buffer_rsrc_t rs, int j)
+{
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int voff = PAIRED ? j * 8 + 2048 * (r & 1) : j * 8, soff = PAIRED ? 4096 * (r >> 1) : 2048 * r;
+        const u32x2 t = ((DEFAULT_ROWS >> r) & 1u) ? __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0)
+                                                   : __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 2);
+        dst[r] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
+    }
+}
+// one row of the sixteen a block stores: the default policy if DEFAULT_ROWS has bit `row`, else OTHER_AUX (2 = non-temporal)
+// (`row` is a constant wherever the caller's row loop is unrolled: the select folds, as above)
+template <unsigned DEFAULT_ROWS, int OTHER_AUX>
+__device__ __forceinline__ void store_row_cf(__amdgpu_buffer_rsrc_t ws, unsigned voff, cf a, int row)
+{
+    if ((DEFAULT_ROWS >> row) & 1u) store_cf<0>(ws, voff, a);
+    else store_cf<OTHER_AUX>(ws, voff, a);
+}
 
 // ---- spectrum times H ----
 // v[q] = X[.. + 256 bin_of(q)] as the forward passes leave it; u[r] = conj(X * H) in natural register order r for the first

@@ -16,6 +16,9 @@
 //
 // Build: make -C tools floor_lab        Run: tools/floor_lab [seconds-per-row]
 //                                        tools/floor_lab <seconds-per-row> wide [rounds]: the headline's shape, 8- against 16-byte rows (below)
+//                                        tools/floor_lab <seconds-per-row> rows [rounds] [e3|e4|e5]: the headline's shape, 8-byte rows, which rows
+//                                            are loaded and stored on the default cache policy (below); the last argument names the load mask of the store sweep
+//                                        tools/floor_lab 0 rows pmc: twenty launches each of the n1 / n2 / n4 / n8 `mem` rows and nothing else, for a counter run
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -125,8 +128,11 @@ __global__ __launch_bounds__(256, OCC) void floor_kernel(const cf *__restrict__ 
 // WIDE = true: eight 16-byte accesses per lane, access k = rows 2k (lanes 0-31 of a wave) and 2k+1 (lanes 32-63) at columns
 // 64w + 2(l & 31) and the next; with SWAP the half-wave exchange that leaves every lane with both rows of ONE column
 // (v_permlane32_swap: vdst = the lane's first element, src = its second) is spent on the way in and on the way out, 32 per block.
-// NOV rows at either end of the window are cached normally, the rest nt: 1 = the product (only rows 0 and 15 are shared with a
-// neighbouring block), 2 = what a row PAIR can express, 4, 8 = every row.
+// LROWS: bit r set = row r of the window is loaded on the default cache policy, clear = non-temporal (a 16-byte access takes the default
+// policy when either of its two rows has its bit).  ends(n) = n rows at either end: ends(1) = the product until round 7 (only rows 0 and
+// 15 are shared with a neighbouring block), ends(2) = the product since, ends(8) = every row.  SROWS: the same for the rows stored
+// (row 0 is never stored: its bit means nothing); 0 = every store non-temporal, as the product stores.
+constexpr unsigned ends(int n) { return ((1u << n) - 1u) | (((1u << n) - 1u) << (16 - n)); }
 __device__ __forceinline__ void half_swap(cf &first, cf &second)
 {
     unsigned a[2] = {__float_as_uint(first.x), __float_as_uint(first.y)}, b[2] = {__float_as_uint(second.x), __float_as_uint(second.y)};
@@ -139,7 +145,7 @@ __device__ __forceinline__ void half_swap(cf &first, cf &second)
     second = cf{__uint_as_float(b[0]), __uint_as_float(b[1])};
 }
 
-template <bool WIDE, int NOV, int MODE, bool SWAP>     // MODE 0 mem, 1 dose
+template <bool WIDE, unsigned LROWS, unsigned SROWS, int MODE, bool SWAP>     // MODE 0 mem, 1 dose
 __global__ __launch_bounds__(256, 4) void dealt_kernel(const cf *__restrict__ in, size_t in_elems, unsigned char *__restrict__ out, Shape s, float k,
                                                       pcx::SchedState *__restrict__ sched)
 {
@@ -161,7 +167,7 @@ __global__ __launch_bounds__(256, 4) void dealt_kernel(const cf *__restrict__ in
         if (WIDE) {
 #pragma unroll
             for (int p = 0; p < 8; p++) {
-                const u32x4 t = (2 * p < NOV || 2 * p + 1 >= 16 - NOV) ? __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off, 4096 * p, 0)
+                const u32x4 t = ((LROWS >> (2 * p)) & 3u) ? __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off, 4096 * p, 0)
                                                    : __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off, 4096 * p, 2);
                 v[2 * p] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
                 v[2 * p + 1] = cf{__uint_as_float(t.z), __uint_as_float(t.w)};
@@ -173,7 +179,7 @@ __global__ __launch_bounds__(256, 4) void dealt_kernel(const cf *__restrict__ in
         } else {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const bool plain = r < NOV || r >= 16 - NOV;
+                const bool plain = (LROWS >> r) & 1u;
                 const u32x2 t = plain ? __builtin_amdgcn_raw_buffer_load_b64(rs, lane_off, 2048 * r, 0)
                                       : __builtin_amdgcn_raw_buffer_load_b64(rs, lane_off, 2048 * r, 2);
                 v[r] = cf{__uint_as_float(t.x), __uint_as_float(t.y)};
@@ -196,14 +202,19 @@ __global__ __launch_bounds__(256, 4) void dealt_kernel(const cf *__restrict__ in
             }
             const unsigned vbase = (unsigned)(lane_off - 2048);
 #pragma unroll
-            for (int p = 0; p < 8; p++)
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v[2 * p].x), __float_as_uint(v[2 * p].y), __float_as_uint(v[2 * p + 1].x), __float_as_uint(v[2 * p + 1].y)},
-                                                       ws, (int)(vbase + 4096u * p), 0, 2);
+            for (int p = 0; p < 8; p++) {
+                const u32x4 y = {__float_as_uint(v[2 * p].x), __float_as_uint(v[2 * p].y), __float_as_uint(v[2 * p + 1].x), __float_as_uint(v[2 * p + 1].y)};
+                if ((SROWS >> (2 * p)) & 3u) __builtin_amdgcn_raw_buffer_store_b128(y, ws, (int)(vbase + 4096u * p), 0, 0);      // (folds per row once unrolled: no branch)
+                else __builtin_amdgcn_raw_buffer_store_b128(y, ws, (int)(vbase + 4096u * p), 0, 2);
+            }
         } else {
             const unsigned vbase = (unsigned)(lane_off - 2048);
 #pragma unroll
-            for (int r = 1; r < 16; r++)
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(v[r].x), __float_as_uint(v[r].y)}, ws, (int)(vbase + 2048u * r), 0, 2);
+            for (int r = 1; r < 16; r++) {
+                const u32x2 y = {__float_as_uint(v[r].x), __float_as_uint(v[r].y)};
+                if ((SROWS >> r) & 1u) __builtin_amdgcn_raw_buffer_store_b64(y, ws, (int)(vbase + 2048u * r), 0, 0);
+                else __builtin_amdgcn_raw_buffer_store_b64(y, ws, (int)(vbase + 2048u * r), 0, 2);
+            }
         }
         if (!deal.advance()) break;
         __syncthreads();                 // the slot is rewritten by the next block's publish
@@ -211,10 +222,15 @@ __global__ __launch_bounds__(256, 4) void dealt_kernel(const cf *__restrict__ in
     deal.finish(j);
 }
 
-template <bool WIDE, int NOV, int MODE, bool SWAP>
+template <bool WIDE, unsigned LROWS, unsigned SROWS, int MODE, bool SWAP>
 static double run_dealt(const Shape &s, const cf *in, size_t in_elems, unsigned char *out, double seconds, float k, pcx::SchedState *sched)
 {
-    auto launch = [&]() { hipLaunchKernelGGL((dealt_kernel<WIDE, NOV, MODE, SWAP>), dim3(s.grid), dim3(256), 0, 0, in, in_elems, out, s, k, sched); };
+    auto launch = [&]() { hipLaunchKernelGGL((dealt_kernel<WIDE, LROWS, SROWS, MODE, SWAP>), dim3(s.grid), dim3(256), 0, 0, in, in_elems, out, s, k, sched); };
+    if (seconds <= 0) {      // a counter run: twenty launches, no timing
+        for (int i = 0; i < 20; i++) launch();
+        CK(hipDeviceSynchronize());
+        return 0;
+    }
     for (int i = 0; i < 200; i++) launch();
     CK(hipDeviceSynchronize());
     hipEvent_t e0, e1;
@@ -283,6 +299,7 @@ int main(int argc, char **argv)
     const Shape fr{"fir255 (255 taps, 64 Mi) for scale", 4, 1024, 16, 3840, 8, 3840, 1, 661, 3, (C + 3839) / 3840, 16.0 * C};
     printf("%-38s %-10s %10s %8s %8s\n", "shape", "row", "ms/launch", "GB/s", "of 8 TB/s");
     auto row = [&](const Shape &s, const char *what, double ms) {
+        if (ms <= 0) { printf("%-38s %-10s (launched, not timed)\n", s.name, what); return; }
         printf("%-38s %-10s %10.4f %8.0f %8.4f\n", s.name, what, ms, s.alg_bytes / ms / 1e6, s.alg_bytes / ms / 1e6 / 8000.0);
         fflush(stdout);
     };
@@ -324,7 +341,7 @@ int main(int argc, char **argv)
         t.name = "fir255 dealt";
         for (int r = 0; r < rounds; r++) {
             row(t, "mem", run<4, 16>(t, 0, in, C + 4096, out, seconds, 1e-3f));           // the grid-stride row of the table above
-#define DEALT_ROW(NAME, WIDE, NOV, MODE, SWAP) row(t, NAME, run_dealt<WIDE, NOV, MODE, SWAP>(t, in, C + 4096, out, seconds, 1e-3f, sched))
+#define DEALT_ROW(NAME, WIDE, NOV, MODE, SWAP) row(t, NAME, run_dealt<WIDE, ends(NOV), 0u, MODE, SWAP>(t, in, C + 4096, out, seconds, 1e-3f, sched))
             DEALT_ROW("mem8 n1", false, 1, 0, false);            // the product's accesses
             DEALT_ROW("mem8 n2", false, 2, 0, false);
             DEALT_ROW("mem16 n2", true, 2, 0, false);            // 16-byte rows, the same policy per row pair
@@ -339,6 +356,50 @@ int main(int argc, char **argv)
             DEALT_ROW("dose8 n4", false, 4, 1, false);
 #undef DEALT_ROW
         }
+        return 0;
+    }
+    if (argc > 2 && std::string(argv[2]) == "rows") {
+        // tools/floor_lab <seconds> rows [rounds] [e3|e4|e5]: the headline's shape, 8-byte rows, by WHICH rows take the default cache policy;
+        // the rows interleaved round by round (profiles/r08/floor_row_policy.txt)
+        const bool pmc = argc > 3 && std::string(argv[3]) == "pmc";
+        const int rounds = pmc ? 1 : argc > 3 ? atoi(argv[3]) : 4;
+        const std::string sbase = argc > 4 ? argv[4] : "e4";
+        pcx::SchedState *sched;
+        CK(hipMalloc(&sched, 4096));
+        CK(hipMemset(sched, 0, 4096));
+        Shape t = fr;
+        t.nblocks = C / 3840;            // full blocks only: every window inside the buffer, every output row whole
+        t.alg_bytes = 16.0 * 3840 * t.nblocks;
+        t.name = "fir255 dealt";
+#define ROWS_ROW(NAME, LROWS, SROWS, MODE) row(t, NAME, run_dealt<false, LROWS, SROWS, MODE, false>(t, in, C + 4096, out, pmc ? 0.0 : seconds, 1e-3f, sched))
+#define ROWS_BOTH(NAME, LROWS, SROWS) do { ROWS_ROW("mem8 " NAME, LROWS, SROWS, 0); if (!pmc) ROWS_ROW("dose8 " NAME, LROWS, SROWS, 1); } while (0)
+        for (int r = 0; r < rounds; r++) {
+            // n default-policy rows at either end
+            ROWS_BOTH("n1", ends(1), 0u);
+            ROWS_BOTH("n2", ends(2), 0u);            // the product
+            ROWS_BOTH("n4", ends(4), 0u);
+            ROWS_BOTH("n8", ends(8), 0u);
+            if (pmc) break;
+            ROWS_BOTH("n3", ends(3), 0u);
+            ROWS_BOTH("n5", ends(5), 0u);
+            ROWS_BOTH("n6", ends(6), 0u);
+            // the same COUNT elsewhere: eight rows as 4 + 4 (n4 above), as every other row (0 2 4 6 9 11 13 15), as 2 + 6 and as 6 + 2;
+            // four rows as 2 + 2 (n2 above) and as 1 + 2 in the middle + 1; eight rows as 1 + 6 in the middle + 1
+            ROWS_BOTH("alt8", 0xAA55u, 0u);
+            ROWS_BOTH("2+6", 0xFC03u, 0u);
+            ROWS_BOTH("6+2", 0xC03Fu, 0u);
+            ROWS_BOTH("1+mid2+1", 0x8181u, 0u);
+            ROWS_BOTH("1+mid6+1", 0x87E1u, 0u);
+            // stored rows on the default policy, with the load mask named on the command line: the four / eight at the ends of the
+            // fifteen stored rows (1 2 14 15 / 1-4 12-15), and all fifteen
+#define STORE_SWEEP(TAG, LROWS) do { ROWS_BOTH(TAG " st4", LROWS, 0xC006u); ROWS_BOTH(TAG " st8", LROWS, 0xF01Eu); ROWS_BOTH(TAG " st15", LROWS, 0xFFFEu); } while (0)
+            if (sbase == "e3") STORE_SWEEP("n3", ends(3));
+            else if (sbase == "e5") STORE_SWEEP("n5", ends(5));
+            else STORE_SWEEP("n4", ends(4));
+#undef STORE_SWEEP
+        }
+#undef ROWS_BOTH
+#undef ROWS_ROW
         return 0;
     }
     for (int m = 0; m < 3; m++) row(fr, names[m], run<4, 16>(fr, m, in, C + 4096, out, seconds, 1e-3f));
