@@ -506,6 +506,44 @@ PCX_API int pcx_threshold_states(pcx_threshold *h, const void *in, size_t n, uns
 PCX_API int pcx_threshold_states_dev(pcx_threshold *h, const void *in_dev, size_t n, unsigned char *states_dev, void *stream);
 
 /* ===================================================================== *
+ *  /comms/signal_probe      utility/SignalProbe.cpp
+ *
+ *  One number from a window of the stream (:123-163): the last element (VALUE, :141), sqrt(sum |x|^2 / N) (RMS, :142-153) or
+ *  sum x / N (MEAN, :154-160), with every element converted to double resp. std::complex<double> first.  A value is a PAIR of doubles
+ *  (re, im); im is 0 for a real stream and for RMS.  The reference adds in stream order; the device adds over one fixed tree that
+ *  depends on the element type and the window's length alone, so a window's pair is the same bit for bit at any byte
+ *  address, anywhere in a batch and from run to run, and within (ceil(log2 N) + 2) u sum |x| / N of the exact mean resp.
+ *  (ceil(log2 N) + 6) u of the exact RMS, u = 2^-53.  The rate limit, the mode strings and the signals are the block's (probe_blocks.cpp).
+ * ===================================================================== */
+typedef struct pcx_probe pcx_probe;
+enum { PCX_PROBE_VALUE = 0, PCX_PROBE_RMS = 1, PCX_PROBE_MEAN = 2 };
+/* signalProbeFactory (:176-188): scalar in {F64, F32, I64, I32, I16, I8}, real or complex; anything else is PCX_ERR_ARG "unsupported
+ * type".  Mode VALUE, window 1024 (:64-67).  Where a device can be reached the scratch of the large-window path is allocated here,
+ * once; otherwise at the first call that computes. */
+PCX_API int pcx_probe_create(pcx_probe **out, int scalar, int is_complex);
+PCX_API int pcx_probe_destroy(pcx_probe *h);
+/* setMode / getMode (:87-95) for the three modes that calculate: any other code is PCX_ERR_ARG (a block keeps an unknown string itself) */
+PCX_API int pcx_probe_set_mode(pcx_probe *h, int mode);
+PCX_API int pcx_probe_get_mode(const pcx_probe *h, int *mode);
+/* setWindow / getWindow (:97-106); 0 is PCX_ERR_ARG (the reference would read x[-1], :141) */
+PCX_API int pcx_probe_set_window(pcx_probe *h, size_t window);
+PCX_API int pcx_probe_get_window(const pcx_probe *h, size_t *window);
+/* in elements of the handle's type: the longest window a workgroup reduces alone (up to a quarter of it a wave does), the slice
+ * of a longer window that a workgroup reduces to a partial, and the shortest window that takes the large-window path (the seams a
+ * test wants to straddle) */
+PCX_API int pcx_probe_get_geometry(const pcx_probe *h, size_t *tile, size_t *slice, size_t *switch_over);
+/* work() (:123-163) on in[0 .. n): N = min(window, n) elements are reduced, value_re_im receives the pair and *consumed = N.  With
+ * N == 0 nothing is consumed and the pair is left as it is.  process takes host pointers (staged, or in place when page-locked) and
+ * returns with the pair in host memory; process_dev takes device pointers, leaves the pair in device memory, allocates nothing and
+ * synchronises nothing: it can be captured into a graph.  Checked in this order before any device call: the handle, consumed, the
+ * pair, in. */
+PCX_API int pcx_probe_process(pcx_probe *h, const void *in, size_t n, double *value_re_im, size_t *consumed);
+PCX_API int pcx_probe_process_dev(pcx_probe *h, const void *in_dev, size_t n, double *value_re_im_dev, size_t *consumed, void *stream);
+/* the batch: ceil(n / window) pairs, pair k what process returns for in[k window .. min((k + 1) window, n)), bit for bit */
+PCX_API int pcx_probe_windows(pcx_probe *h, const void *in, size_t n, double *values);
+PCX_API int pcx_probe_windows_dev(pcx_probe *h, const void *in_dev, size_t n, double *values_dev, void *stream);
+
+/* ===================================================================== *
  *  /comms/preamble_framer      digital/PreambleFramer.cpp
  *  /comms/frame_insert         digital/FrameInsert.cpp, digital/FrameHelper.hpp
  *

@@ -79,6 +79,8 @@ PCXB_API int pcxb_get_bytes(pcxb_block *b, const char *name, unsigned char *out,
 PCXB_API int pcxb_call_complex(pcxb_block *b, const char *name, double re, double im);
 PCXB_API int pcxb_get_complex(pcxb_block *b, const char *name, double *re, double *im);
 PCXB_API int pcxb_get_double(pcxb_block *b, const char *name, double *out);
+/* a registered call without an argument whose result is not wanted: a slot such as "probeValue" of /comms/signal_probe */
+PCXB_API int pcxb_call_void(pcxb_block *b, const char *name);
 PCXB_API int pcxb_get_size(pcxb_block *b, const char *name, size_t *out);
 PCXB_API int pcxb_get_int64(pcxb_block *b, const char *name, int64_t *out);
 PCXB_API int pcxb_get_bool(pcxb_block *b, const char *name, int *out);
@@ -118,6 +120,9 @@ PCXB_API int pcxb_circular_create(size_t bytes, void **base, size_t *actual);
 PCXB_API int pcxb_circular_destroy(void *base);
 /* the reserve a block asked for at construction time (FFT: numBins); SIZE_MAX = none */
 PCXB_API int pcxb_initial_reserve(pcxb_block *b, size_t *reserve);
+/* the reserve input 0 stands at now: what the constructor, a setter (setWindow of /comms/signal_probe) or the last work() asked for;
+ * SIZE_MAX = none */
+PCXB_API int pcxb_input_reserve(pcxb_block *b, size_t *reserve);
 
 /*
  * One work() call: plant `in` (in_elems elements, labels attached) and `out` (room for

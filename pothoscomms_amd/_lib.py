@@ -38,6 +38,7 @@ REPACK_BITS_TO_SYMBOLS, REPACK_SYMBOLS_TO_BITS, REPACK_BYTES_TO_SYMBOLS, REPACK_
 WAVE_CONST, WAVE_SINE, WAVE_RAMP, WAVE_SQUARE = 0, 1, 2, 3                       # pcx_waveform_table
 NOISE_UNIFORM, NOISE_NORMAL, NOISE_LAPLACE, NOISE_POISSON = 0, 1, 2, 3           # pcx_noise_table
 NOISE_ENTRIES = 4096
+PROBE_VALUE, PROBE_RMS, PROBE_MEAN = 0, 1, 2                                     # pcx_probe_set_mode
 FRAME_OTHER, FRAME_START, FRAME_END = 0, 1, 2                                    # pcx_frame_event.kind
 SEG_INPUT, SEG_POOL, SEG_HEADER, SEG_ZERO = 0, 1, 2, 3                           # pcx_frame_segment.kind
 FRAME_HEADER_BITS = 58
@@ -213,6 +214,17 @@ SIGNATURES = {
     "pcx_threshold_process_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
     "pcx_threshold_states": (_i, [_vp, _vp, _sz, _vp]),
     "pcx_threshold_states_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "pcx_probe_create": (_i, [C.POINTER(_vp), _i, _i]),
+    "pcx_probe_destroy": (_i, [_vp]),
+    "pcx_probe_set_mode": (_i, [_vp, _i]),
+    "pcx_probe_get_mode": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_probe_set_window": (_i, [_vp, _sz]),
+    "pcx_probe_get_window": (_i, [_vp, _psz]),
+    "pcx_probe_get_geometry": (_i, [_vp, _psz, _psz, _psz]),
+    "pcx_probe_process": (_i, [_vp, _vp, _sz, _vp, _psz]),
+    "pcx_probe_process_dev": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
+    "pcx_probe_windows": (_i, [_vp, _vp, _sz, _vp]),
+    "pcx_probe_windows_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "pcx_framer_create": (_i, [C.POINTER(_vp), _i, _i]),
     "pcx_framer_destroy": (_i, [_vp]),
     "pcx_framer_set_preamble": (_i, [_vp, _vp, _sz, _sz, _i]),

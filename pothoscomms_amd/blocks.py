@@ -64,14 +64,16 @@ _blib = None
 # /comms/const_comparator, /comms/const_arithmetic, /comms/bitwise_unary, /comms/bitwise_binary, /comms/const_bitwise_binary,
 # /comms/bitshift, /comms/byte_order), "math" libpcx_math_blocks.so (math_blocks.cpp: /comms/exp, exp2, exp10, expm1, expN, log, log2, log10,
 # log1p, logN, pow, sqrt, cbrt, nth_root, rsqrt, sinc, sigmoid, trigonometric), "special" libpcx_special_blocks.so (special_blocks.cpp:
-# /comms/gamma, lngamma, erf, erfc, beta, modf) -- one registry each, as Pothos loads one module library per source directory
+# /comms/gamma, lngamma, erf, erfc, beta, modf), "probe" libpcx_probe_blocks.so (probe_blocks.cpp: /comms/signal_probe, a block without
+# an output port) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
            "symbol": os.path.join(_HERE, "libpcx_symbol_blocks.so"), "repack": os.path.join(_HERE, "libpcx_repack_blocks.so"),
            "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so"),
            "framer": os.path.join(_HERE, "libpcx_framer_blocks.so"), "logic": os.path.join(_HERE, "libpcx_logic_blocks.so"),
-           "math": os.path.join(_HERE, "libpcx_math_blocks.so"), "special": os.path.join(_HERE, "libpcx_special_blocks.so")}
+           "math": os.path.join(_HERE, "libpcx_math_blocks.so"), "special": os.path.join(_HERE, "libpcx_special_blocks.so"),
+           "probe": os.path.join(_HERE, "libpcx_probe_blocks.so")}
 _mlibs = {}
 
 
@@ -118,6 +120,8 @@ def load(module="comms"):
     L.pcxb_call_complex.argtypes = [vp, cp, C.c_double, C.c_double]
     L.pcxb_get_complex.argtypes = [vp, cp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.pcxb_get_size.argtypes = [vp, cp, C.POINTER(sz)]
+    L.pcxb_call_void.argtypes = [vp, cp]
+    L.pcxb_input_reserve.argtypes = [vp, C.POINTER(sz)]
     L.pcxb_get_bool.argtypes = [vp, cp, C.POINTER(i)]
     L.pcxb_get_string.argtypes = [vp, cp, cp, sz]
     L.pcxb_get_taps.argtypes = [vp, cp, vp, sz, C.POINTER(sz), i]
@@ -242,6 +246,11 @@ class Block:
             self.out_dtype, self.out_dim, _ = self._port(1)
             return
         self.in_dtype, self.in_dim, _ = self._port(0)
+        nout = C.c_size_t()
+        _check_in(self._module, L.pcxb_num_ports(self._h, 1, C.byref(nout)))
+        if nout.value == 0:                   # a sink (/comms/signal_probe): driven through work_ports with no outputs
+            self.out_dtype, self.out_dim = None, 0
+            return
         self.out_dtype, self.out_dim, _ = self._port(1)
 
     def close(self):
@@ -335,6 +344,12 @@ class Block:
             v = C.c_int64()
             _check_in(self._module, L.pcxb_get_int64(self._h, n, C.byref(v)))
             return v.value + (1 << 64) if v.value < 0 and str(self.dtype).startswith("uint") else v.value
+        if name == "value" and not args:        # /comms/signal_probe: a double on a real stream, a std::complex<double> on a complex one
+            re, im = C.c_double(), C.c_double()
+            _check_in(self._module, L.pcxb_get_complex(self._h, n, C.byref(re), C.byref(im)))
+            return complex(re.value, im.value) if str(self.dtype).startswith("complex_") else re.value
+        if name.startswith("probe") and not args:       # a registerProbe slot: emits "<name>Triggered" and returns nothing
+            return self.call_slot(name)
         if name in ("setBase", "setExponent", "setRoot"):       # one value of the stream type (the math module)
             return _check_in(self._module, L.pcxb_call_double(self._h, n, float(args[0])))
         if name in ("base", "exponent", "root") and not args:
@@ -357,7 +372,8 @@ class Block:
             return [int(b) for b in buf[:cnt.value]]
         if not args:   # getter
             if name in ("getThreshold", "getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
-                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus", "getPaddingSize", "getSymbolWidth", "getHeaderId", "shiftSize"):
+                        "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus", "getPaddingSize", "getSymbolWidth", "getHeaderId", "shiftSize",
+                        "getWindow"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value
@@ -366,7 +382,7 @@ class Block:
                 _check_in(self._module, L.pcxb_get_bool(self._h, n, C.byref(v)))
                 return bool(v.value)
             if name in ("getPhase", "getFactor", "sampleRate", "frequencyLower", "frequencyUpper", "bandwidthTrans", "alpha",
-                        "stopDB", "passDB", "gain", "getAttack", "getRelease", "getFrequency", "getSampleRate", "getResolution", "getMean", "getB"):
+                        "stopDB", "passDB", "gain", "getAttack", "getRelease", "getFrequency", "getSampleRate", "getResolution", "getMean", "getB", "getRate"):
                 v = C.c_double()
                 _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
                 return v.value
@@ -381,6 +397,16 @@ class Block:
         if isinstance(a, float):
             return _check_in(self._module, L.pcxb_call_double(self._h, n, a))
         return _check_in(self._module, L.pcxb_call_string(self._h, n, str(a).encode()))
+
+    def call_slot(self, name):
+        """a registered call without an argument whose result is not wanted (a slot such as "probeValue")"""
+        _check_in(self._module, load(self._module).pcxb_call_void(self._h, name.encode()))
+
+    def reserve(self):
+        """the reserve input 0 stands at now (None: none asked for)"""
+        r = C.c_size_t()
+        _check_in(self._module, load(self._module).pcxb_input_reserve(self._h, C.byref(r)))
+        return None if r.value == _SIZE_MAX else r.value
 
     def calls(self):
         """{name: number of arguments} of the calls the block registered"""

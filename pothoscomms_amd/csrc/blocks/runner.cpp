@@ -201,6 +201,7 @@ int pcxb_get_complex(pcxb_block *b, const char *name, double *re, double *im)
     });
 }
 int pcxb_get_double(pcxb_block *b, const char *name, double *out) { return guarded([&] { *out = b->blk->call(name).convert<double>(); }); }
+int pcxb_call_void(pcxb_block *b, const char *name) { return guarded([&] { (void)b->blk->call(name); }); }
 int pcxb_get_size(pcxb_block *b, const char *name, size_t *out) { return guarded([&] { *out = b->blk->call(name).convert<unsigned long>(); }); }
 int pcxb_get_int64(pcxb_block *b, const char *name, int64_t *out) { return guarded([&] { *out = (int64_t)b->blk->call(name).convert<long long>(); }); }
 int pcxb_get_bool(pcxb_block *b, const char *name, int *out) { return guarded([&] { *out = b->blk->call(name).convert<bool>() ? 1 : 0; }); }
@@ -270,6 +271,13 @@ int pcxb_link_buffer(pcxb_block *src, pcxb_block *dst, size_t min_bytes, void **
     });
 }
 int pcxb_initial_reserve(pcxb_block *b, size_t *reserve) { *reserve = b->initialReserve; return PCX_OK; }
+int pcxb_input_reserve(pcxb_block *b, size_t *reserve)
+{
+    return guarded([&] {
+        const InputPort *ip = b->blk->input(0);
+        *reserve = ip->_reserveSet ? ip->_reserve : std::numeric_limits<size_t>::max();
+    });
+}
 
 // ---- the framework's circular buffer: one pageable shared-memory object mapped twice back to back ----
 static std::mutex g_circ_mutex;

@@ -341,6 +341,13 @@ int launch_thr_slice(const ThrShape &p, const void *in, void *out, size_t m, con
 int launch_thr_empty(const ThrWork &w, uint64_t *counts_out, hipStream_t st);
 // the state after each of the m elements, one byte each; the carried state is the entry state of the first slice and stays as it is
 int launch_thr_states(const ThrShape &p, const void *in, size_t m, const ThrWork &w, int first, unsigned char *states, hipStream_t st);
+// (probe.hip) /comms/signal_probe: windows of W elements reduced to one pair of doubles each over the fixed tree of DESIGN.md 22
+size_t probe_tile(int scalar, bool cplx);   // elements of the longest window a workgroup reduces alone, and of a slice of a longer one
+size_t probe_slice(int scalar, bool cplx);
+size_t probe_max_slices();                  // partials the scratch of a handle holds: pairs of doubles
+// ceil(n / W) windows of the n elements at `in`, the last one the remainder: values receives a pair (re, im) per window.  mode:
+// PCX_PROBE_VALUE / RMS / MEAN.  part: probe_max_slices() pairs of scratch, used when W exceeds probe_tile()
+int launch_probe_windows(int scalar, bool cplx, int mode, const void *in, size_t n, size_t W, double *values, double *part, hipStream_t st);
 // (splice.hip) /comms/preamble_framer, /comms/frame_insert: one entry of the segment table as the kernel reads it
 struct SpliceSeg {
     uint64_t dst;                           // first output byte

@@ -76,6 +76,11 @@ def _dev_ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _any_dev_ptr(t):
+    """a device tensor, or a raw device address (an int: a view at a byte offset no tensor type can express)"""
+    return C.c_void_p(t) if isinstance(t, int) else _dev_ptr(t)
+
+
 def _gate_ptr(t):
     """a gate word: device memory, or page-locked host memory (the device reads it in place; the host opens it with a plain store)"""
     if not t.is_cuda and t.is_pinned():
@@ -692,6 +697,81 @@ class Threshold(_Handle):
 
     def states_dev(self, x, n, states, stream=None):
         _lib.check(_lib.load().pcx_threshold_states_dev(self._h, _dev_ptr(x), n, _dev_ptr(states), _stream_ptr(stream)))
+
+
+class SignalProbe(_Handle):
+    """pcx_probe_*: utility/SignalProbe.cpp's value of a window of the stream -- its last element (VALUE), sqrt(sum |x|^2 / N) (RMS) or
+    sum x / N (MEAN), in double precision over a fixed summation tree.  A value is a float on a real stream and a
+    complex on a complex one; the *_dev forms leave pairs of doubles (re, im) in device memory."""
+    _destroy = "pcx_probe_destroy"
+    MODES = {"VALUE": _lib.PROBE_VALUE, "RMS": _lib.PROBE_RMS, "MEAN": _lib.PROBE_MEAN}
+
+    def __init__(self, dtype="complex_float32", mode="VALUE", window=1024):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, self.is_complex = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_probe_create(C.byref(self._h), self.scalar, int(self.is_complex)))
+        self.np_dtype = np.dtype(NP_SCALAR[self.scalar])
+        self.set_mode(mode)
+        self.set_window(window)
+
+    def set_mode(self, mode):
+        if mode not in self.MODES:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "signal probe: unknown mode %r" % (mode,))
+        _lib.check(_lib.load().pcx_probe_set_mode(self._h, self.MODES[mode]))
+        self.mode = mode
+
+    def set_window(self, window):
+        _lib.check(_lib.load().pcx_probe_set_window(self._h, int(window)))
+
+    @property
+    def window(self):
+        v = C.c_size_t()
+        _lib.check(_lib.load().pcx_probe_get_window(self._h, C.byref(v)))
+        return v.value
+
+    def geometry(self):
+        """(tile, slice, switch_over) in elements: the longest window of the small-window path, the slice of a longer window that a
+        workgroup reduces to a partial, the shortest window of the large-window path"""
+        v = [C.c_size_t() for _ in range(3)]
+        _lib.check(_lib.load().pcx_probe_get_geometry(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def _elements(self, x):
+        x = as_pairs(x)
+        if x.dtype != self.np_dtype or x.ndim != (2 if self.is_complex else 1) or (self.is_complex and x.shape[1] != 2):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "signal probe: %s%s input for a %s probe" % (x.dtype, x.shape, self.dtype))
+        return x
+
+    def _value(self, pair):
+        return complex(pair[0], pair[1]) if self.is_complex else float(pair[0])
+
+    def process(self, x):
+        """one work() call on x: (value, consumed) with consumed = min(window, elements); value is None when nothing was consumed"""
+        x = self._elements(x)
+        v, c = np.zeros(2, np.float64), C.c_size_t()
+        _lib.check(_lib.load().pcx_probe_process(self._h, _np_ptr(x), x.shape[0], _np_ptr(v), C.byref(c)))
+        return (self._value(v) if c.value else None), c.value
+
+    def windows(self, x):
+        """the value of every window of x, the last one the remainder: float64 (real) or complex128 of ceil(n / window) entries"""
+        x = self._elements(x)
+        nw = -(-x.shape[0] // self.window)
+        v = np.zeros((max(nw, 1), 2), np.float64)
+        _lib.check(_lib.load().pcx_probe_windows(self._h, _np_ptr(x), x.shape[0], _np_ptr(v)))
+        v = v[:nw]
+        return v.copy().view(np.complex128).reshape(-1) if self.is_complex else v[:, 0].copy()
+
+    def process_dev(self, x, n, value, stream=None):
+        """device tensors (or raw device addresses): n elements at x, value two float64 that receive (re, im); returns what the call
+        consumed; nothing is allocated or synchronised"""
+        c = C.c_size_t()
+        _lib.check(_lib.load().pcx_probe_process_dev(self._h, _any_dev_ptr(x), n, _any_dev_ptr(value), C.byref(c), _stream_ptr(stream)))
+        return c.value
+
+    def windows_dev(self, x, n, values, stream=None):
+        """device tensors (or raw device addresses): values receives ceil(n / window) pairs of float64"""
+        _lib.check(_lib.load().pcx_probe_windows_dev(self._h, _any_dev_ptr(x), n, _any_dev_ptr(values), _stream_ptr(stream)))
 
 
 class Framer(_Handle):
