@@ -292,6 +292,16 @@ PCX_API int pcx_fft_destroy(pcx_fft *h);
  * FFT.cpp:66-71; a device caller batches whole frames per call). */
 PCX_API int pcx_fft_transform(pcx_fft *h, const void *in, void *out, size_t nframes);
 PCX_API int pcx_fft_transform_dev(pcx_fft *h, const void *in_dev, void *out_dev, size_t nframes, void *stream);
+/* pcx_fft_get_plan: which plan pcx_fft_create chose for (scalar, num_bins).  IDENTITY: one bin.  R16_4096 / R16 / POW2: one workgroup
+ * per group of frames, radix 16 or radix 2 / 4 in LDS.  Q15_POW2 / Q15_GLOBAL: kiss_fft's Q15 stages in LDS / one launch per stage
+ * over global memory.  MIXED: kissfft's factor order in LDS.  SMOOTH: 2^a 3^b 5^c bins, 16s first.  FOURSTEP / FOURSTEP_SHORT:
+ * num_bins = n1 * n2 around two shorter plans / around the column and row kernels.  BLUESTEIN: chirp-z on power-of-two plans. */
+enum { PCX_FFT_PLAN_IDENTITY = 0, PCX_FFT_PLAN_R16_4096 = 1, PCX_FFT_PLAN_R16 = 2, PCX_FFT_PLAN_POW2 = 3, PCX_FFT_PLAN_Q15_POW2 = 4,
+       PCX_FFT_PLAN_Q15_GLOBAL = 5, PCX_FFT_PLAN_MIXED = 6, PCX_FFT_PLAN_SMOOTH = 7, PCX_FFT_PLAN_FOURSTEP = 8,
+       PCX_FFT_PLAN_FOURSTEP_SHORT = 9, PCX_FFT_PLAN_BLUESTEIN = 10 };
+/* *kind = the plan; *n1, *n2 = the split num_bins = n1 * n2 of the two four-step plans; for BLUESTEIN *n1 = num_bins and *n2 = M, the
+ * power-of-two convolution size; 0 and 0 for every other plan.  Makes no device call. */
+PCX_API int pcx_fft_get_plan(const pcx_fft *h, int *kind, size_t *n1, size_t *n2);
 
 /* ===================================================================== *
  *  /comms/freq_demod      demod/FreqDemod.cpp

@@ -30,6 +30,8 @@ OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4
 # pcx_fir_algo
 FIR_AUTO, FIR_DIRECT, FIR_OLS_FFT, FIR_EXACT = 0, 1, 2, 3
 IIR_SCAN, IIR_SERIAL = 0, 1          # pcx_iir_get_plan
+# pcx_fft_get_plan: PCX_FFT_PLAN_*, in the order of the handle's kinds
+FFT_PLANS = ("IDENTITY", "R16_4096", "R16", "POW2", "Q15_POW2", "Q15_GLOBAL", "MIXED", "SMOOTH", "FOURSTEP", "FOURSTEP_SHORT", "BLUESTEIN")
 SCR_ADDITIVE, SCR_MULTIPLICATIVE = 0, 1     # pcx_scrambler_set_mode
 SCR_SCAN, SCR_SERIAL = 0, 1          # pcx_scrambler_get_plan
 PRE_PLANES, PRE_BYTES = 0, 1         # pcx_preamble_get_plan
@@ -143,6 +145,7 @@ SIGNATURES = {
     "pcx_fft_destroy": (_i, [_vp]),
     "pcx_fft_transform": (_i, [_vp, _vp, _vp, _sz]),
     "pcx_fft_transform_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "pcx_fft_get_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_sz), C.POINTER(_sz)]),
     "pcx_freqdemod_create": (_i, [_i, C.POINTER(_vp)]),
     "pcx_freqdemod_destroy": (_i, [_vp]),
     "pcx_freqdemod_reset": (_i, [_vp]),

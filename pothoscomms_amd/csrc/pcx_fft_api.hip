@@ -101,12 +101,19 @@ int pcx_fft_create(int scalar, size_t num_bins, int inverse, pcx_fft **out)
         size_t M = 1;
         while (M < 2 * num_bins - 1) M <<= 1;
         h->n1 = num_bins; h->n2 = M;
-        // w[n] = exp(-j pi n^2 / N), n^2 reduced modulo 2N so the phase is exact for any N
+        // w[n] = exp(-j pi n^2 / N), n^2 reduced modulo 2N so the phase is exact for any N.  The quadrant is taken out in integers as
+        // well, pi r / N = q pi / 2 + a with a in [0, pi / 2), and a goes through the long-double cos / sin: a double phase of up to
+        // 2 pi carries a rounding of up to 9 units of the double result, which the complex_float64 plan then shows on an impulse
+        // (24 u against kissfft's 6 u; tests/test_fft_plans_gpu.py) -- each output is a product of three chirp entries
         std::vector<double> w(2 * num_bins), b(2 * M, 0.0);
         for (size_t n = 0; n < num_bins; n++) {
             const unsigned long long r = ((unsigned long long)n * (unsigned long long)n) % (2ull * num_bins);
-            const double ph = -3.141592653589793238462643383279502884 * (double)r / (double)num_bins;
-            w[2 * n] = std::cos(ph); w[2 * n + 1] = std::sin(ph);
+            const unsigned long long q = 2 * r / num_bins, rem = 2 * r - q * num_bins;
+            const long double a = 1.570796326794896619231321691639751442L * (long double)rem / (long double)num_bins;
+            const double c = (double)std::cos(a), s = (double)std::sin(a);
+            // exp(-j (q pi / 2 + a))
+            w[2 * n] = q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s;
+            w[2 * n + 1] = q == 0 ? -s : q == 1 ? -c : q == 2 ? s : c;
             // conjugate chirp, wrapped: b[n] = b[M - n] = conj(w[n])
             b[2 * n] = w[2 * n]; b[2 * n + 1] = -w[2 * n + 1];
             if (n) { b[2 * (M - n)] = w[2 * n]; b[2 * (M - n) + 1] = -w[2 * n + 1]; }
@@ -274,6 +281,20 @@ int pcx_fft_create(int scalar, size_t num_bins, int inverse, pcx_fft **out)
     return PCX_OK;
 }
 int pcx_fft_destroy(pcx_fft *h) { delete h; return PCX_OK; }
+static_assert(pcx_fft::IDENTITY == PCX_FFT_PLAN_IDENTITY && pcx_fft::R16_4096 == PCX_FFT_PLAN_R16_4096 && pcx_fft::R16 == PCX_FFT_PLAN_R16 &&
+              pcx_fft::POW2 == PCX_FFT_PLAN_POW2 && pcx_fft::Q15_POW2 == PCX_FFT_PLAN_Q15_POW2 && pcx_fft::Q15_GLOBAL == PCX_FFT_PLAN_Q15_GLOBAL &&
+              pcx_fft::MIXED == PCX_FFT_PLAN_MIXED && pcx_fft::SMOOTH == PCX_FFT_PLAN_SMOOTH && pcx_fft::FOURSTEP == PCX_FFT_PLAN_FOURSTEP &&
+              pcx_fft::FOURSTEP_SHORT == PCX_FFT_PLAN_FOURSTEP_SHORT && pcx_fft::BLUESTEIN == PCX_FFT_PLAN_BLUESTEIN,
+              "PCX_FFT_PLAN_* (include/pcx.h) follow pcx_fft::Kind");
+int pcx_fft_get_plan(const pcx_fft *h, int *kind, size_t *n1, size_t *n2)
+{
+    PCX_CHECK_ARG(h, "null handle");
+    PCX_CHECK_ARG(kind && n1 && n2, "null out");
+    *kind = (int)h->kind;
+    *n1 = h->n1;
+    *n2 = h->n2;
+    return PCX_OK;
+}
 
 // The plans that go through workspaces (four-step, chirp-z) take a long call in batches of frames, so that the workspaces stay
 // at kFftWorkspaceCap bytes each whatever the call: a 34 GB call of 20486-bin frames would otherwise ask for 2 x 110 GB

@@ -237,6 +237,12 @@ class Fft(_Handle):
     def transform_dev(self, x, y, nframes, stream=None):
         _lib.check(_lib.load().pcx_fft_transform_dev(self._h, _dev_ptr(x), _dev_ptr(y), nframes, _stream_ptr(stream)))
 
+    def plan(self):
+        """pcx_fft_get_plan: (name of the plan, n1, n2) -- the four-step split, or (num_bins, M) of the chirp-z plan, else 0, 0"""
+        k, n1, n2 = C.c_int(), C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.load().pcx_fft_get_plan(self._h, C.byref(k), C.byref(n1), C.byref(n2)))
+        return _lib.FFT_PLANS[k.value], n1.value, n2.value
+
 
 class FreqDemod(_Handle):
     """pcx_freqdemod_*: demod/FreqDemod.cpp:44-71 with _prev carried on the device."""
