@@ -629,6 +629,85 @@ PCX_API int pcx_framer_process_dev(pcx_framer *h, const void *in_dev, size_t n_i
                                    size_t out_cap, pcx_frame_plan *plan, unsigned char *used, uint64_t *insert_at, uint64_t *shift, void *stream);
 
 /* ===================================================================== *
+ *  /comms/frame_sync           digital/FrameSync.cpp, digital/FrameHelper.hpp
+ *
+ *  The receiver of /comms/frame_insert's frame: it searches the stream for the sync word (every preamble symbol held symbol_width *
+ *  data_width samples), estimates scale, frequency offset and phase there, reads the 58 BPSK header symbols behind it and passes the
+ *  payload on: as it is but scaled (RAW), turned back by the estimated carrier (PHASE), also resampled to one element per data symbol
+ *  (TIMING), or from the sync word on (DEBUG).  One call is one work() of the reference; the state it carries from call to call lives in
+ *  the handle and activate() resets it.  DESIGN.md 24 has the method and the places where the port differs (symbol widths below 3; a
+ *  sync word of at most 65536 samples).  The handle keeps no history of the stream: a frame may begin in front of the buffer of the call
+ *  that declares it, but neither the reference nor this port reads anything there.  All device arithmetic is double for both element types.
+ * ===================================================================== */
+typedef struct pcx_fsync pcx_fsync;
+enum { PCX_FSYNC_RAW = 0, PCX_FSYNC_PHASE = 1, PCX_FSYNC_TIMING = 2, PCX_FSYNC_DEBUG = 3 };            /* the output mode */
+enum { PCX_FSYNC_PHASE_OFFSET = 0, PCX_FSYNC_FRAME_START = 1, PCX_FSYNC_FRAME_END = 2 };               /* pcx_fsync_label.kind, label ids */
+/* a label the call posts on its output: index and width in output elements from the call's first.  value: the phase in radians
+ * (PHASE_OFFSET); length: the header's length field (all three kinds) */
+typedef struct pcx_fsync_label {
+    uint32_t kind, reserved;
+    uint64_t index, width, length;
+    double value;
+} pcx_fsync_label;
+typedef struct pcx_fsync_result {
+    uint64_t consumed, produced;      /* input elements consumed, output elements written */
+    uint64_t reserve;                 /* the input port's reserve after the call (it stays until a later call changes it) */
+    uint32_t n_labels, reserved;
+    pcx_fsync_label labels[3];        /* in the order they are posted: phase offset, frame start, frame end */
+    /* the state after the call */
+    uint64_t remaining;               /* payload elements still to come (input elements); 0: searching */
+    double phase, phase_inc;          /* the carrier phase at the next payload element, and its step per input element */
+    double scale, delta_fc, phase_off;/* the estimates at the last correlation maximum */
+    uint64_t max_peak, count_since_max;
+} pcx_fsync_result;
+/* (scalar, is_complex) in {(PCX_F32, 1), (PCX_F64, 1)}, anything else is PCX_ERR_ARG "unsupported type".  The constructor's settings
+ * (:185-193): mode RAW, preamble {1}, header id 0x55, symbol width 20, data width 4, input threshold 0.01, frame start id "frameStart",
+ * the other two ids empty. */
+PCX_API int pcx_fsync_create(pcx_fsync **out, int scalar, int is_complex);
+PCX_API int pcx_fsync_destroy(pcx_fsync *h);
+/* an unknown mode, an empty preamble, a data width below 2 and a negative threshold are PCX_ERR_ARG as they are exceptions in the
+ * reference (:202, :217, :251, :293).  A symbol width below 3 is PCX_ERR_ARG too: the reference takes 1 and 2 and then averages over
+ * an empty or wrapped window.  A sync word (symbol width * data width * preamble symbols) beyond 65536 samples is
+ * PCX_ERR_ARG as well, which the reference does not know: one lane walks the word once per candidate frame.  The threshold is kept in
+ * the stream's precision.  A setter touches no device; where a width or the preamble changed, the next call waits for the handle's
+ * enqueued calls and uploads the preamble. */
+PCX_API int pcx_fsync_set_output_mode(pcx_fsync *h, int mode);
+PCX_API int pcx_fsync_get_output_mode(const pcx_fsync *h, int *mode);
+PCX_API int pcx_fsync_set_preamble(pcx_fsync *h, const void *symbols, size_t count);
+PCX_API int pcx_fsync_get_preamble(const pcx_fsync *h, void *symbols, size_t cap, size_t *count);
+PCX_API int pcx_fsync_set_header_id(pcx_fsync *h, unsigned char id);
+PCX_API int pcx_fsync_get_header_id(const pcx_fsync *h, unsigned char *id);
+PCX_API int pcx_fsync_set_symbol_width(pcx_fsync *h, size_t width);
+PCX_API int pcx_fsync_get_symbol_width(const pcx_fsync *h, size_t *width);
+PCX_API int pcx_fsync_set_data_width(pcx_fsync *h, size_t width);
+PCX_API int pcx_fsync_get_data_width(const pcx_fsync *h, size_t *width);
+PCX_API int pcx_fsync_set_input_threshold(pcx_fsync *h, double threshold);
+PCX_API int pcx_fsync_get_input_threshold(const pcx_fsync *h, double *threshold);
+/* accepted and kept; nothing is printed */
+PCX_API int pcx_fsync_set_verbose(pcx_fsync *h, int enable);
+/* the id of the labels of `kind`; an empty id (or NULL) means that the label is not posted.  get copies at most cap bytes, the
+ * terminator included, and sets *len to the id's length */
+PCX_API int pcx_fsync_set_label_id(pcx_fsync *h, int kind, const char *id);
+PCX_API int pcx_fsync_get_label_id(const pcx_fsync *h, int kind, char *id, size_t cap, size_t *len);
+/* the derived settings (updateSettings, :342-348): the sync word and the frame head in samples, the two correlation thresholds; the
+ * offsets a workgroup of the search kernel owns; and the offsets of the first piece of a search call -- a call correlates its offsets in
+ * pieces, each twice as long as the one before, and stops behind the piece in which a frame is found (the seams a test wants to
+ * straddle) */
+PCX_API int pcx_fsync_get_geometry(const pcx_fsync *h, size_t *sync_width, size_t *frame_width, size_t *corr_mag, size_t *corr_dur, size_t *tile,
+                                   size_t *first_piece);
+/* activate() (:326-333): back to searching, phase and tracker cleared; the reported estimates and the reserve are cleared too (the
+ * reference leaves those members as they are; it reads none of them before it has set them) */
+PCX_API int pcx_fsync_activate(pcx_fsync *h);
+/* one work() on n_in input elements with room for out_cap output elements.  While a payload remains the call only enqueues: nothing
+ * is read back and process_dev does not synchronise.  A SEARCH call reads a few words back per candidate frame and therefore waits
+ * for the stream before it returns.  No form can be captured into a graph: the handle's state advances on the host.  in and out must
+ * not share a byte.  process takes host pointers (staged, or in place when page-locked); process_dev device pointers, at any 8-byte
+ * (complex_float32) or 16-byte (complex_float64) aligned address.  Checked in this order before any device call: the handle, the
+ * result, in, out. */
+PCX_API int pcx_fsync_process(pcx_fsync *h, const void *in, size_t n_in, void *out, size_t out_cap, pcx_fsync_result *result);
+PCX_API int pcx_fsync_process_dev(pcx_fsync *h, const void *in_dev, size_t n_in, void *out_dev, size_t out_cap, pcx_fsync_result *result, void *stream);
+
+/* ===================================================================== *
  *  /comms/symbol_mapper      digital/SymbolMapper.cpp
  *
  *  out[i] = map[in[i] & mask] (:89-91): one unsigned char in, one element of the stream type out.  Exact.

@@ -96,6 +96,19 @@ class FramePlan(C.Structure):
                 ("n_headers", C.c_uint64), ("cut", C.c_int)]
 
 
+class FsyncLabel(C.Structure):
+    """pcx_fsync_label: a label a frame sync call posts on its output."""
+    _fields_ = [("kind", C.c_uint32), ("reserved", C.c_uint32), ("index", C.c_uint64), ("width", C.c_uint64), ("length", C.c_uint64),
+                ("value", C.c_double)]
+
+
+class FsyncResult(C.Structure):
+    """pcx_fsync_result: what a frame sync call did and the state it leaves."""
+    _fields_ = [("consumed", C.c_uint64), ("produced", C.c_uint64), ("reserve", C.c_uint64), ("n_labels", C.c_uint32), ("reserved", C.c_uint32),
+                ("labels", FsyncLabel * 3), ("remaining", C.c_uint64), ("phase", C.c_double), ("phase_inc", C.c_double), ("scale", C.c_double),
+                ("delta_fc", C.c_double), ("phase_off", C.c_double), ("max_peak", C.c_uint64), ("count_since_max", C.c_uint64)]
+
+
 _vp, _sz, _i, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_double
 _psz = C.POINTER(C.c_size_t)
 
@@ -241,6 +254,27 @@ SIGNATURES = {
     "pcx_framer_plan": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz]),
     "pcx_framer_process": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     "pcx_framer_process_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "pcx_fsync_create": (_i, [C.POINTER(_vp), _i, _i]),
+    "pcx_fsync_destroy": (_i, [_vp]),
+    "pcx_fsync_set_output_mode": (_i, [_vp, _i]),
+    "pcx_fsync_get_output_mode": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_fsync_set_preamble": (_i, [_vp, _vp, _sz]),
+    "pcx_fsync_get_preamble": (_i, [_vp, _vp, _sz, _psz]),
+    "pcx_fsync_set_header_id": (_i, [_vp, C.c_ubyte]),
+    "pcx_fsync_get_header_id": (_i, [_vp, C.POINTER(C.c_ubyte)]),
+    "pcx_fsync_set_symbol_width": (_i, [_vp, _sz]),
+    "pcx_fsync_get_symbol_width": (_i, [_vp, _psz]),
+    "pcx_fsync_set_data_width": (_i, [_vp, _sz]),
+    "pcx_fsync_get_data_width": (_i, [_vp, _psz]),
+    "pcx_fsync_set_input_threshold": (_i, [_vp, _d]),
+    "pcx_fsync_get_input_threshold": (_i, [_vp, C.POINTER(_d)]),
+    "pcx_fsync_set_verbose": (_i, [_vp, _i]),
+    "pcx_fsync_set_label_id": (_i, [_vp, _i, C.c_char_p]),
+    "pcx_fsync_get_label_id": (_i, [_vp, _i, C.c_char_p, _sz, _psz]),
+    "pcx_fsync_get_geometry": (_i, [_vp, _psz, _psz, _psz, _psz, _psz, _psz]),
+    "pcx_fsync_activate": (_i, [_vp]),
+    "pcx_fsync_process": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(FsyncResult)]),
+    "pcx_fsync_process_dev": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(FsyncResult), _vp]),
     "pcx_mapper_create": (_i, [_i, _i, C.POINTER(_vp)]),
     "pcx_mapper_destroy": (_i, [_vp]),
     "pcx_mapper_set_map": (_i, [_vp, _vp, _sz]),

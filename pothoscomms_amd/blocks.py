@@ -65,7 +65,7 @@ _blib = None
 # /comms/bitshift, /comms/byte_order), "math" libpcx_math_blocks.so (math_blocks.cpp: /comms/exp, exp2, exp10, expm1, expN, log, log2, log10,
 # log1p, logN, pow, sqrt, cbrt, nth_root, rsqrt, sinc, sigmoid, trigonometric), "special" libpcx_special_blocks.so (special_blocks.cpp:
 # /comms/gamma, lngamma, erf, erfc, beta, modf), "probe" libpcx_probe_blocks.so (probe_blocks.cpp: /comms/signal_probe, a block without
-# an output port) -- one registry each, as Pothos loads one module library per source directory
+# an output port), "framesync" libpcx_framesync_blocks.so (framesync_blocks.cpp: /comms/frame_sync) -- one registry each, as Pothos loads one module library per source directory
 MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filter_blocks.so"),
            "envelope": os.path.join(_HERE, "libpcx_envelope_blocks.so"), "iir": os.path.join(_HERE, "libpcx_iir_blocks.so"),
            "digital": os.path.join(_HERE, "libpcx_digital_blocks.so"), "correlator": os.path.join(_HERE, "libpcx_correlator_blocks.so"),
@@ -73,7 +73,7 @@ MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filte
            "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so"),
            "framer": os.path.join(_HERE, "libpcx_framer_blocks.so"), "logic": os.path.join(_HERE, "libpcx_logic_blocks.so"),
            "math": os.path.join(_HERE, "libpcx_math_blocks.so"), "special": os.path.join(_HERE, "libpcx_special_blocks.so"),
-           "probe": os.path.join(_HERE, "libpcx_probe_blocks.so")}
+           "probe": os.path.join(_HERE, "libpcx_probe_blocks.so"), "framesync": os.path.join(_HERE, "libpcx_framesync_blocks.so")}
 _mlibs = {}
 
 
@@ -373,7 +373,7 @@ class Block:
         if not args:   # getter
             if name in ("getThreshold", "getDecimation", "getInterpolation", "getNumInlineBuffers", "numTaps", "getShardPasses", "getDevice", "getPortSlabBytes",
                         "getAverageSize", "getCascadeSize", "getLookahead", "getSymbols", "getModulus", "getPaddingSize", "getSymbolWidth", "getHeaderId", "shiftSize",
-                        "getWindow"):
+                        "getWindow", "getDataWidth"):
                 v = C.c_size_t()
                 _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
                 return v.value
@@ -382,7 +382,7 @@ class Block:
                 _check_in(self._module, L.pcxb_get_bool(self._h, n, C.byref(v)))
                 return bool(v.value)
             if name in ("getPhase", "getFactor", "sampleRate", "frequencyLower", "frequencyUpper", "bandwidthTrans", "alpha",
-                        "stopDB", "passDB", "gain", "getAttack", "getRelease", "getFrequency", "getSampleRate", "getResolution", "getMean", "getB", "getRate"):
+                        "stopDB", "passDB", "gain", "getAttack", "getRelease", "getFrequency", "getSampleRate", "getResolution", "getMean", "getB", "getRate", "getInputThreshold"):
                 v = C.c_double()
                 _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
                 return v.value

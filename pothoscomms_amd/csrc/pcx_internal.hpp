@@ -359,6 +359,37 @@ size_t splice_lds_segments();               // the longest slice of the table a 
 // preamble symbol (complex_float32 in the first 8 bytes)
 int launch_splice(size_t es, const void *in, const void *pool, const SpliceSeg *segs, size_t nseg, const uint64_t *headers, void *out, size_t total,
                   const unsigned char sym[16], hipStream_t st);
+// (framesync.hip) /comms/frame_sync: the settings of a configured handle as the kernels read them, and what they leave behind
+struct FsyncShape {
+    bool f64 = false;                       // complex_float64, else complex_float32
+    size_t sw = 20, dw = 4, P = 1;          // symbol width, data width, preamble symbols
+    size_t W = 80, F = 80 + 58 * 4;         // samples of the sync word, and of the sync word with the header
+    double thresh = 0;                      // the input threshold, in the stream's precision
+    double abs_front = 1, abs_back = 1;     // |preamble.front()|, |preamble.back()|
+};
+struct FsyncEst {
+    double scale = 0, delta_fc = 0, phase_off = 0;
+};
+struct FsyncScanOut {                       // the tracker after its last offset, or at the offset `at` where it declares a frame
+    uint64_t declared, at, max_peak, count, peak_idx;       // peak_idx: ~0 when the maximum is the carried one
+};
+struct FsyncFinishOut {
+    double scale, delta_fc, phase_off;      // the estimates at the peak
+    uint64_t first_bit, bits, found;        // the sampling offset of the first header bit, the 58 bits, whether the search found its peak
+};
+size_t fsync_tile();                        // offsets per workgroup of the metric kernel
+// corrPeak of the offsets [first, N) of x[0 .. n), N <= n - F + 1 and first a multiple of fsync_tile(); pre: P pairs of doubles on the
+// device; flags: one word per tile of fsync_tile() offsets, whether one of its corrPeaks exceeds thresh
+int launch_fsync_metric(const FsyncShape &s, const void *x, size_t n, size_t first, size_t N, const double *pre, uint32_t thresh, uint32_t *peaks,
+                        uint32_t *flags, hipStream_t st);
+// the tracker over peaks[s0 .. N) from the carried (max0, cnt0); flags: those of the tiles in front of N
+int launch_fsync_scan(const uint32_t *peaks, const uint32_t *flags, uint64_t s0, uint64_t N, uint32_t thresh, uint64_t dur, uint32_t max0, uint64_t cnt0,
+                      FsyncScanOut *out, hipStream_t st);
+// behind a scan, from its record on the device: the estimates at a maximum of this launch (else `carried`) and, where a frame is declared,
+// the first-bit search and the header bits.  Offsets count from x[0]
+int launch_fsync_finish(const FsyncShape &s, const void *x, size_t n, const double *pre, const FsyncEst &carried, const FsyncScanOut *scan,
+                        FsyncFinishOut *out, hipStream_t st);
+int launch_fsync_payload(bool f64, int mode, const void *in, void *out, size_t N, size_t dw, double scale, double phase0, double inc, hipStream_t st);
 // (symbols.hip) /comms/symbol_mapper, /comms/symbol_slicer, /comms/differential_encoder, /comms/differential_decoder
 struct DiffShape {
     int decode = 0;

@@ -930,6 +930,153 @@ class Framer(_Handle):
         return self.Result(None, plan, used[:n], at[:n], shift[:n])
 
 
+class FrameSync(_Handle):
+    """pcx_fsync_*: digital/FrameSync.cpp (complex_float32, complex_float64) -- the search for /comms/frame_insert's sync word, the
+    header behind it and the payload behind that.  One call is one work() of the reference; the handle carries its state
+    and activate() resets it.  A call returns a Result: the output, what was consumed and produced, the port's reserve, the labels
+    [(kind, index, width, value)] with kind in {"phase_offset", "frame_start", "frame_end"} (value: the phase, else the length) and
+    the state after the call."""
+    _destroy = "pcx_fsync_destroy"
+    MODES = ("RAW", "PHASE", "TIMING", "DEBUG")
+    LABEL_KINDS = ("phase_offset", "frame_start", "frame_end")
+
+    class Result:
+        def __init__(self, out, r):
+            self.out, self.consumed, self.produced, self.reserve = out, r.consumed, r.produced, r.reserve
+            self.labels = [(FrameSync.LABEL_KINDS[l.kind], l.index, l.width, l.value if l.kind == 0 else l.length) for l in r.labels[:r.n_labels]]
+            self.remaining, self.phase, self.phase_inc = r.remaining, r.phase, r.phase_inc
+            self.scale, self.delta_fc, self.phase_off = r.scale, r.delta_fc, r.phase_off
+            self.max_peak, self.count_since_max = r.max_peak, r.count_since_max
+
+    def __init__(self, dtype="complex_float32", output_mode="RAW", preamble=(1,), header_id=0x55, symbol_width=20, data_width=4,
+                 input_threshold=0.01, frame_start_id="frameStart", frame_end_id="", phase_offset_id=""):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, self.cplx = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_fsync_create(C.byref(self._h), self.scalar, int(self.cplx)))
+        self.np_dtype = np.dtype(NP_SCALAR[self.scalar])
+        self.set_output_mode(output_mode)
+        self.set_symbol_width(symbol_width)
+        self.set_data_width(data_width)
+        self.set_preamble(preamble)
+        self.set_header_id(header_id)
+        self.set_input_threshold(input_threshold)
+        self.set_label_ids(frame_start_id, frame_end_id, phase_offset_id)
+
+    def _typed(self, a, what):
+        a = np.asarray(a)
+        if a.ndim == 1:
+            a = a.astype(np.complex64 if self.scalar == F32 else np.complex128)
+        a = as_pairs(a)
+        if a.dtype != self.np_dtype or a.ndim != 2 or a.shape[1] != 2:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "frame sync: %s %s%s for a %s block" % (what, a.dtype, a.shape, self.dtype))
+        return np.ascontiguousarray(a)
+
+    def set_output_mode(self, mode):
+        if mode not in self.MODES:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "FrameSync::setOutputMode(%s): unknown output mode" % (mode,))
+        _lib.check(_lib.load().pcx_fsync_set_output_mode(self._h, self.MODES.index(mode)))
+
+    def output_mode(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_fsync_get_output_mode(self._h, C.byref(v)))
+        return self.MODES[v.value]
+
+    def set_preamble(self, preamble):
+        p = self._typed(np.asarray(preamble), "preamble")
+        _lib.check(_lib.load().pcx_fsync_set_preamble(self._h, _np_ptr(p) if p.size else None, p.shape[0]))
+
+    def preamble(self):
+        n = C.c_size_t()
+        _lib.check(_lib.load().pcx_fsync_get_preamble(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 2), self.np_dtype)
+        _lib.check(_lib.load().pcx_fsync_get_preamble(self._h, _np_ptr(out), n.value, C.byref(n)))
+        return out
+
+    def set_header_id(self, header_id):
+        _lib.check(_lib.load().pcx_fsync_set_header_id(self._h, int(header_id) & 0xFF))
+
+    def header_id(self):
+        v = C.c_ubyte()
+        _lib.check(_lib.load().pcx_fsync_get_header_id(self._h, C.byref(v)))
+        return v.value
+
+    def set_symbol_width(self, width):
+        _lib.check(_lib.load().pcx_fsync_set_symbol_width(self._h, int(width)))
+
+    def symbol_width(self):
+        v = C.c_size_t()
+        _lib.check(_lib.load().pcx_fsync_get_symbol_width(self._h, C.byref(v)))
+        return v.value
+
+    def set_data_width(self, width):
+        _lib.check(_lib.load().pcx_fsync_set_data_width(self._h, int(width)))
+
+    def data_width(self):
+        v = C.c_size_t()
+        _lib.check(_lib.load().pcx_fsync_get_data_width(self._h, C.byref(v)))
+        return v.value
+
+    def set_input_threshold(self, threshold):
+        _lib.check(_lib.load().pcx_fsync_set_input_threshold(self._h, float(threshold)))
+
+    def input_threshold(self):
+        v = C.c_double()
+        _lib.check(_lib.load().pcx_fsync_get_input_threshold(self._h, C.byref(v)))
+        return v.value
+
+    def set_verbose(self, enable):
+        _lib.check(_lib.load().pcx_fsync_set_verbose(self._h, int(bool(enable))))
+
+    def set_label_ids(self, frame_start_id=None, frame_end_id=None, phase_offset_id=None):
+        """None leaves an id as it is; an empty id switches the label off"""
+        for kind, v in ((1, frame_start_id), (2, frame_end_id), (0, phase_offset_id)):
+            if v is not None:
+                _lib.check(_lib.load().pcx_fsync_set_label_id(self._h, kind, str(v).encode()))
+
+    def label_ids(self):
+        """(frame_start_id, frame_end_id, phase_offset_id)"""
+        out = []
+        for kind in (1, 2, 0):
+            n = C.c_size_t()
+            _lib.check(_lib.load().pcx_fsync_get_label_id(self._h, kind, None, 0, C.byref(n)))
+            buf = C.create_string_buffer(n.value + 1)
+            _lib.check(_lib.load().pcx_fsync_get_label_id(self._h, kind, buf, n.value + 1, C.byref(n)))
+            out.append(buf.value.decode())
+        return tuple(out)
+
+    def geometry(self):
+        """(sync_width, frame_width, corr_mag, corr_dur, tile, first_piece): the derived settings, the offsets a workgroup of the search
+        owns and the offsets of a search call's first piece"""
+        v = [C.c_size_t() for _ in range(6)]
+        _lib.check(_lib.load().pcx_fsync_get_geometry(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def activate(self):
+        _lib.check(_lib.load().pcx_fsync_activate(self._h))
+
+    def process(self, x, out_cap=None, out=None):
+        """x: the call's input as a numpy array; out_cap: room of the output in elements (default: as many as the input)"""
+        x = self._typed(x, "input")
+        if out_cap is None:
+            out_cap = x.shape[0] if out is None else out.shape[0]
+        if out is None:
+            out = np.zeros((max(1, out_cap), 2), self.np_dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == self.np_dtype and out.flags.c_contiguous and out.shape[0] >= out_cap and out.shape[1:] == (2,)):
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "frame sync: out must be a contiguous %s array with room for out_cap elements" % self.np_dtype)
+        r = _lib.FsyncResult()
+        _lib.check(_lib.load().pcx_fsync_process(self._h, _np_ptr(x) if x.shape[0] else None, x.shape[0], _np_ptr(out), out_cap, C.byref(r)))
+        return self.Result(out[:r.produced], r)
+
+    def process_dev(self, x, n_in, out, out_cap, stream=None):
+        """device memory x and out (torch tensors used as memory, or raw addresses); returns the Result without output.  A search call
+        waits for the stream, a payload call only enqueues"""
+        r = _lib.FsyncResult()
+        _lib.check(_lib.load().pcx_fsync_process_dev(self._h, _any_dev_ptr(x) if n_in else None, n_in, _any_dev_ptr(out) if out_cap else None, out_cap,
+                                                     C.byref(r), _stream_ptr(stream)))
+        return self.Result(None, r)
+
+
 class _SymbolMap(_Handle):
     """what pcx_mapper_* and pcx_slicer_* share: a map in the stream type's own element layout"""
     _family = None
