@@ -233,6 +233,31 @@ PCX_API int pcx_fir_set_qformat(pcx_fir *h, const pcx_qformat *q);
 PCX_API int pcx_fir_get_geometry(const pcx_fir *h, size_t *K, size_t *input_require);
 /* which algorithm the last process call ran (pcx_fir_algo) */
 PCX_API int pcx_fir_last_algo(const pcx_fir *h);
+/* pcx_fir_get_last_plan: which plan the last process call ran -- one value per branch of the choice pcx_fir_process_dev makes from the
+ * handle's tables (pcx_fir_last_algo has three values; most plans report PCX_FIR_OLS_FFT).  NONE: no call has run yet.  A name says
+ * which kernel ran and on which table layout: branches that launch one kernel with different tables have names of their own.
+ *   CF32_OLS4096 / _GATED  complex_float32, M = L = 1, K <= 2049: the 4096-sample kernel; _GATED its launch behind a gate word
+ *   CF32_UPOLS             the same stream, 2049 < K <= 8193: the partitioned kernel
+ *   CF32_DECIM / _INTERP   complex_float32, the spectrum folded (M = 2 or 4- / 8- / 16-fold) / replicated (L in 2, 4, 8, 16)
+ *   CF32_OLS4096_ROWS      complex_float32, M = 1, other L: every polyphase row through the 4096-sample kernel, then interleaved
+ *   CF32_POLY              complex_float32, other (L, M): the polyphase kernel with strided stores
+ *   F32_OLS4096 / F32_UPOLS / F32_OLS4096_ROWS   real float32: two real blocks per transform; its halves side by side through the
+ *                          partitioned kernel beyond 2049 taps; its polyphase rows (L > 1, rows of up to 2049 taps)
+ *   UPOLS_ROWS / UPOLS_DECIM   float32 or complex_float32: polyphase rows of 2050 .. 8193 taps / decimators (complex beyond 2049
+ *                          taps, real of any length) through the partitioned kernel
+ *   CF64_OLS / CF64_OLS_ROWS   complex_float64, complex_int16, complex_int8 on the double pipeline; its polyphase rows (L > 1)
+ *   REAL64_OLS / REAL64_OLS_ROWS   real float64, int16, int8: two real blocks per double transform; its polyphase rows
+ *   CF32_DIRECT_TILE       the LDS-tiled time-domain kernel (complex_float32, M = L = 1)
+ *   DOT2 / SLIDE / GENERIC the time-domain kernels of every type: packed 16-bit dot products (complex_int16 / complex_int8, M = L = 1),
+ *                          the sliding window (M = L = 1), one output per lane (any L, M)
+ * It makes no device call. */
+enum { PCX_FIR_PLAN_NONE = 0, PCX_FIR_PLAN_CF32_OLS4096 = 1, PCX_FIR_PLAN_CF32_OLS4096_GATED = 2, PCX_FIR_PLAN_CF32_UPOLS = 3,
+       PCX_FIR_PLAN_CF32_DECIM = 4, PCX_FIR_PLAN_CF32_INTERP = 5, PCX_FIR_PLAN_CF32_OLS4096_ROWS = 6, PCX_FIR_PLAN_CF32_POLY = 7,
+       PCX_FIR_PLAN_F32_OLS4096 = 8, PCX_FIR_PLAN_F32_UPOLS = 9, PCX_FIR_PLAN_F32_OLS4096_ROWS = 10, PCX_FIR_PLAN_UPOLS_ROWS = 11,
+       PCX_FIR_PLAN_UPOLS_DECIM = 12, PCX_FIR_PLAN_CF64_OLS = 13, PCX_FIR_PLAN_CF64_OLS_ROWS = 14, PCX_FIR_PLAN_REAL64_OLS = 15,
+       PCX_FIR_PLAN_REAL64_OLS_ROWS = 16, PCX_FIR_PLAN_CF32_DIRECT_TILE = 17, PCX_FIR_PLAN_DOT2 = 18, PCX_FIR_PLAN_SLIDE = 19,
+       PCX_FIR_PLAN_GENERIC = 20 };
+PCX_API int pcx_fir_get_last_plan(const pcx_fir *h, int *plan);
 /* How many of the device's 1024 resident workgroup slots the handle's persistent launches may take (a multiple of 128; default
  * 1024 = the whole device).  For handles that run SIDE BY SIDE on one device -- several shards of a stream on one GPU, two filter
  * blocks of one topology -- so that their launches share the device instead of queueing behind one another's workgroups

@@ -29,6 +29,10 @@ SPEC_FN = dict(zip(("GAMMA", "LNGAMMA", "ERF", "ERFC"), range(4)))
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4
 # pcx_fir_algo
 FIR_AUTO, FIR_DIRECT, FIR_OLS_FFT, FIR_EXACT = 0, 1, 2, 3
+# pcx_fir_get_last_plan: PCX_FIR_PLAN_*, in the order of their values
+FIR_PLANS = ("NONE", "CF32_OLS4096", "CF32_OLS4096_GATED", "CF32_UPOLS", "CF32_DECIM", "CF32_INTERP", "CF32_OLS4096_ROWS", "CF32_POLY",
+             "F32_OLS4096", "F32_UPOLS", "F32_OLS4096_ROWS", "UPOLS_ROWS", "UPOLS_DECIM", "CF64_OLS", "CF64_OLS_ROWS", "REAL64_OLS",
+             "REAL64_OLS_ROWS", "CF32_DIRECT_TILE", "DOT2", "SLIDE", "GENERIC")
 IIR_SCAN, IIR_SERIAL = 0, 1          # pcx_iir_get_plan
 # pcx_fft_get_plan: PCX_FFT_PLAN_*, in the order of the handle's kinds
 FFT_PLANS = ("IDENTITY", "R16_4096", "R16", "POW2", "Q15_POW2", "Q15_GLOBAL", "MIXED", "SMOOTH", "FOURSTEP", "FOURSTEP_SHORT", "BLUESTEIN")
@@ -149,6 +153,7 @@ SIGNATURES = {
     "pcx_get_qformat": (_i, [_vp]),
     "pcx_fir_get_geometry": (_i, [_vp, _psz, _psz]),
     "pcx_fir_last_algo": (_i, [_vp]),
+    "pcx_fir_get_last_plan": (_i, [_vp, C.POINTER(_i)]),
     "pcx_fir_set_slots": (_i, [_vp, C.c_uint]),
     "pcx_fir_process": (_i, [_vp, _vp, _sz, _vp, _sz, _psz, _psz]),
     "pcx_fir_process_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _psz, _psz, _vp]),

@@ -14,7 +14,7 @@ struct pcx_fir {
     int scalar = PCX_F32, cplx = 1, ctaps = 1;
     std::vector<double> taps;  // ntaps * (ctaps ? 2 : 1)
     size_t ntaps = 1, M = 1, L = 1, K = 1, inputRequire = 1;
-    int algo = PCX_FIR_AUTO, last_algo = 0;
+    int algo = PCX_FIR_AUTO, last_algo = 0, last_plan = PCX_FIR_PLAN_NONE;
     QFormat qf = kDefaultQFormat;   // integer element types: the floatToQ / fromQ reading (pcx_fir_set_qformat; the process-wide one at creation)
     bool dirty = true;
     DevBuf rowLen, rowTaps, tapsRev, Hspec, tw4096;
@@ -490,6 +490,12 @@ int pcx_fir_get_geometry(const pcx_fir *h, size_t *K, size_t *input_require)
     return PCX_OK;
 }
 int pcx_fir_last_algo(const pcx_fir *h) { return h ? h->last_algo : PCX_ERR_ARG; }
+int pcx_fir_get_last_plan(const pcx_fir *h, int *plan)
+{
+    PCX_CHECK_ARG(h && plan, "null argument");
+    *plan = h->last_plan;
+    return PCX_OK;
+}
 int pcx_fir_set_slots(pcx_fir *h, unsigned slots)
 {
     PCX_CHECK_ARG(h, "null handle");
@@ -606,10 +612,12 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
         rc = launch_fir_cf32_ols4096(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->tw4096.p, h->sched.p, st, gate_word, gate_value, gated, h->slots);
         if (rc != PCX_OK || !*gated) return rc;
         h->last_algo = algo;
+        h->last_plan = PCX_FIR_PLAN_CF32_OLS4096_GATED;
         *consumed = N;
         *produced = n_out;
         return PCX_OK;
     }
+    int plan;     // PCX_FIR_PLAN_* of the branch taken below (pcx_fir_get_last_plan)
     // interpolation through polyphase ROWS: every row filtered at the input rate into a contiguous workspace row, then one
     // interleaving pass.  Long calls go in batches of iterations so that the workspace stays at kRowsWorkspaceCap bytes
     // whatever the call (it would be a second copy of the output otherwise).
@@ -626,43 +634,55 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
         return PCX_OK;
     };
     if (algo == PCX_FIR_OLS_FFT && h->have_interp_f32) {
+        plan = PCX_FIR_PLAN_F32_OLS4096_ROWS;
         rc = rows_path(4, h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
             return launch_fir_f32_ols4096(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HspecRows.p) + jr * 2 * 4096 * sizeof(float), h->K,
                                           h->tw4096.p, h->sched.p, st);
         });
     } else if (algo == PCX_FIR_OLS_FFT && h->have_interp_real) {
+        plan = PCX_FIR_PLAN_REAL64_OLS_ROWS;
         rc = rows_path(fir_elem_bytes(h), h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
             return launch_fir_real_ols(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HrowsD.p) + jr * 2 * 4096 * sizeof(double), h->K, 12,
                                        h->tw4096.p, h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : h->scalar == PCX_I8 ? 2 : 3, 1, qs, st);
         });
     } else if (algo == PCX_FIR_OLS_FFT && h->have_interp64) {
+        plan = PCX_FIR_PLAN_CF64_OLS_ROWS;
         rc = rows_path(fir_elem_bytes(h), h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
             return launch_fir_cf64_ols(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HrowsD.p) + jr * 2 * 4096 * sizeof(double), h->K, 12,
                                        h->tw4096.p, h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : 2, 1, qs, st);
         });
     } else if (algo == PCX_FIR_OLS_FFT && h->have_ols_real64) {
+        plan = PCX_FIR_PLAN_REAL64_OLS;
         rc = launch_fir_real_ols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, h->ols_log2n, h->tw4096.p,
                                  h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : h->scalar == PCX_I8 ? 2 : 3, h->M, qs, st, h->sched.p);
     } else if (algo == PCX_FIR_OLS_FFT && (h->have_ols64 || h->have_ols_int)) {
+        plan = PCX_FIR_PLAN_CF64_OLS;
         rc = launch_fir_cf64_ols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, h->ols_log2n, h->tw4096.p,
                                  h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : 2, h->M, qs, st, h->sched.p);
     } else if (algo == PCX_FIR_OLS_FFT && h->have_upols_rows) {
+        plan = PCX_FIR_PLAN_UPOLS_ROWS;
         const size_t tb = fir_upols_table_bytes(h->ols_parts);
         rc = rows_path(fir_elem_bytes(h), h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
             return launch_fir_cf32_upols(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HspecRows.p) + jr * tb, h->K, h->ols_parts, h->tw4096.p, st,
                                          !h->cplx, 1);
         });
     } else if (algo == PCX_FIR_OLS_FFT && h->have_upols_decim) {
+        plan = PCX_FIR_PLAN_UPOLS_DECIM;
         rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, h->ols_parts, h->tw4096.p, st, !h->cplx, h->M);
     } else if (algo == PCX_FIR_OLS_FFT && h->have_real_ols && h->ols_parts != 0) {
+        plan = PCX_FIR_PLAN_F32_UPOLS;
         rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->ols_parts, h->tw4096.p, st, true);
     } else if (algo == PCX_FIR_OLS_FFT && h->have_real_ols) {
+        plan = PCX_FIR_PLAN_F32_OLS4096;
         rc = launch_fir_f32_ols4096(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->tw4096.p, h->sched.p, st);
     } else if (algo == PCX_FIR_OLS_FFT && h->have_interp) {
+        plan = PCX_FIR_PLAN_CF32_INTERP;
         rc = launch_fir_cf32_ols4096_interp(in_dev, used_in, out_dev, N, h->Hdecim.p, h->K, h->L, h->tw4096.p, h->sched.p, st);
     } else if (algo == PCX_FIR_OLS_FFT && h->have_decim) {
+        plan = PCX_FIR_PLAN_CF32_DECIM;
         rc = launch_fir_cf32_ols4096_decim(in_dev, used_in, out_dev, N, h->Hdecim.p, h->K, h->M, h->tw4096.p, h->sched.p, st);
     } else if (algo == PCX_FIR_OLS_FFT && h->have_poly && h->M == 1 && h->K <= 2049 && !PCX_ENV_SET("PCX_FIR_POLY_STRIDED")) {
+        plan = PCX_FIR_PLAN_CF32_OLS4096_ROWS;
         // interpolation by other factors: each polyphase row through the undecimated kernel into a contiguous workspace row,
         // then one interleaving pass (PCX_FIR_POLY_STRIDED (A/B) keeps the polyphase kernel's stride-L stores)
         rc = rows_path(8, 1, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
@@ -670,12 +690,16 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
                                            h->tw4096.p, h->sched.p, st);
         });
     } else if (algo == PCX_FIR_OLS_FFT && h->have_poly) {
+        plan = PCX_FIR_PLAN_CF32_POLY;
         rc = launch_fir_cf32_ols4096_poly(in_dev, used_in, out_dev, N, h->HspecRows.p, h->K, h->L, h->M, h->tw4096.p, st);
     } else if (algo == PCX_FIR_OLS_FFT && h->ols_parts != 0) {
+        plan = PCX_FIR_PLAN_CF32_UPOLS;
         rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->ols_parts, h->tw4096.p, st);
     } else if (algo == PCX_FIR_OLS_FFT) {
+        plan = PCX_FIR_PLAN_CF32_OLS4096;
         rc = launch_fir_cf32_ols4096(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->tw4096.p, h->sched.p, st, nullptr, 0, nullptr, h->slots, h->lead_valid);
     } else if (algo == PCX_FIR_DIRECT && fast && (2048 + h->Kp + 8) * 9 / 8 * 8 + 64 <= 64 * 1024) {
+        plan = PCX_FIR_PLAN_CF32_DIRECT_TILE;
         // the LDS-tiled time-domain kernel while its tile (2048 outputs + taps) fits; longer filters than every
         // fast plan (K > 8193) take the sliding-window kernel below
         rc = launch_fir_cf32_direct(in_dev, used_in, out_dev, n_out, h->tapsRev.p, h->K, h->Kp, st);
@@ -686,14 +710,15 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
         // PCX_FIR_DOT2=0 keeps complex_int16 on the 24-bit multiply path (A/B)
         const int dot2 = (int)PCX_ENV_INT("PCX_FIR_DOT2", 1);
         if (slide && dot2 && h->taps16 && h->L == 1 && h->M == 1 && h->K <= 12000)
-            rc = launch_fir_ci16_dot2(in_dev, out_dev, n_out, h->K, h->tapsP.p, h->scalar == PCX_I8, qs, st);
+            plan = PCX_FIR_PLAN_DOT2, rc = launch_fir_ci16_dot2(in_dev, out_dev, n_out, h->K, h->tapsP.p, h->scalar == PCX_I8, qs, st);
         else if (slide && h->L == 1 && h->M == 1)
-            rc = launch_fir_slide(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, h->taps24, g, in_dev, out_dev, n_out, qs, st);
+            plan = PCX_FIR_PLAN_SLIDE, rc = launch_fir_slide(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, h->taps24, g, in_dev, out_dev, n_out, qs, st);
         else
-            rc = launch_fir_generic(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, g, in_dev, out_dev, n_out, qs, st);
+            plan = PCX_FIR_PLAN_GENERIC, rc = launch_fir_generic(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, g, in_dev, out_dev, n_out, qs, st);
     }
     if (rc != PCX_OK) return rc;
     h->last_algo = algo;
+    h->last_plan = plan;
     *consumed = N;
     *produced = n_out;
     return PCX_OK;

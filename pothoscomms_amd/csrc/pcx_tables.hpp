@@ -120,6 +120,46 @@ inline std::vector<T> make_hspec(const std::vector<std::complex<double>> &h, siz
     }
     return H;
 }
+// The same spectrum for the double-precision plans (fir_ols_f64.hip; N a power of two).  Their outputs are doubles, so the table's own
+// error shows at full weight: the sum above, K terms one after another in double, is about 0.3 sqrt(K) u off -- the error of the
+// reference's time-domain sum, which a frequency-domain plan need not have (complex_float64 at 4097 taps measured 19 u on noise and
+// 15 u on an impulse against the 5 u and 6 u of a plain overlap-save; tests/test_fir_truth_gpu.py).  So: a radix-2 transform in long
+// double, every twiddle the cos / sin of its own angle, rounded to double once (N log2 N operations instead of N K).
+template <>
+inline std::vector<double> make_hspec<double>(const std::vector<std::complex<double>> &h, size_t N, size_t advance)
+{
+    using LD = long double;
+    const LD two_pi = 6.283185307179586476925286766559005768L;
+    std::vector<LD> wr(N), wi(N), ar(N, 0), ai(N, 0);
+    for (size_t i = 0; i < N; i++) { const LD a = two_pi * (LD)i / (LD)N; wr[i] = std::cos(a); wi[i] = -std::sin(a); }    // exp(-j 2 pi i / N)
+    int bits = 0;
+    while (((size_t)1 << bits) < N) bits++;
+    for (size_t k = 0; k < h.size(); k++) {      // bit-reversed order for the decimation-in-time passes (a filter longer than N wraps)
+        size_t r = 0;
+        for (int b = 0; b < bits; b++) r |= (((k & (N - 1)) >> b) & 1) << (bits - 1 - b);
+        ar[r] += (LD)h[k].real(); ai[r] += (LD)h[k].imag();
+    }
+    for (size_t half = 1; half < N; half *= 2)
+        for (size_t g = 0; g < N; g += 2 * half)
+            for (size_t j = 0; j < half; j++) {
+                const size_t e = j * (N / (2 * half)), lo = g + j, hi = lo + half;
+                const LD tr = ar[hi] * wr[e] - ai[hi] * wi[e], ti = ar[hi] * wi[e] + ai[hi] * wr[e];
+                ar[hi] = ar[lo] - tr; ai[hi] = ai[lo] - ti;
+                ar[lo] += tr; ai[lo] += ti;
+            }
+    std::vector<double> H(2 * N);
+    for (size_t b = 0; b < N; b++) {
+        LD sr = ar[b], si = ai[b];
+        if (advance) {
+            const size_t e = (N - (b * advance) % N) % N;
+            const LD pr = sr * wr[e] - si * wi[e], pi = sr * wi[e] + si * wr[e];
+            sr = pr; si = pi;
+        }
+        H[2 * b] = (double)(sr / (LD)N);
+        H[2 * b + 1] = (double)(si / (LD)N);
+    }
+    return H;
+}
 inline std::vector<float> make_hspec4096(const std::vector<std::complex<double>> &h) { return make_hspec(h, 4096); }
 // The resampling kernels (fir_ols_decim.hip) re-read H from L2 in every block, so their copy is stored the way their lanes hold the
 // spectrum (fft4096.hpp, spec_lane): entry j + 256 r is bin (j >> 4) + 16 (j & 15) + 256 r, and a wave still reads whole 512-byte rows

@@ -152,6 +152,13 @@ class FirFilter(_Handle):
     def last_algo(self):
         return _lib.load().pcx_fir_last_algo(self._h)
 
+    @property
+    def last_plan(self):
+        """pcx_fir_get_last_plan: the name (_lib.FIR_PLANS) of the plan the last call ran, "NONE" before the first"""
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_fir_get_last_plan(self._h, C.byref(v)))
+        return _lib.FIR_PLANS[v.value]
+
     def set_slots(self, slots):
         """pcx_fir_set_slots: the share of the device's 1024 resident workgroup slots this handle's launches take"""
         _lib.check(_lib.load().pcx_fir_set_slots(self._h, int(slots)))

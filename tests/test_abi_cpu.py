@@ -18,7 +18,7 @@ def header_symbols():
 
 def test_header_declares_the_expected_entry_points():
     syms = header_symbols()
-    for must in ("pcx_fir_create", "pcx_fir_set_taps", "pcx_fir_process", "pcx_fir_process_dev", "pcx_fft_create",
+    for must in ("pcx_fir_create", "pcx_fir_set_taps", "pcx_fir_process", "pcx_fir_process_dev", "pcx_fir_get_last_plan", "pcx_fft_create",
                  "pcx_fft_transform_dev", "pcx_freqdemod_process_dev", "pcx_rotate_dev", "pcx_scale_dev", "pcx_abs_dev",
                  "pcx_conj_dev", "pcx_fmchain_process_dev", "pcx_last_error"):
         assert must in syms
@@ -84,6 +84,10 @@ def test_factory_and_setter_argument_errors(pcx):
     c, p = C.c_size_t(7), C.c_size_t(7)
     assert L.pcx_fir_process_dev(h, None, 10, None, 100, C.byref(c), C.byref(p), None) == 0
     assert (c.value, p.value) == (0, 0)
+    # the plan of the last call: none has run; a null handle or a null result is an argument error
+    plan = C.c_int(-1)
+    assert L.pcx_fir_get_last_plan(h, C.byref(plan)) == 0 and plan.value == 0 and pcx._lib.FIR_PLANS[0] == "NONE"
+    assert L.pcx_fir_get_last_plan(None, C.byref(plan)) == pcx._lib.ERR_ARG and L.pcx_fir_get_last_plan(h, None) == pcx._lib.ERR_ARG
     assert L.pcx_fir_destroy(h) == 0
     f = C.c_void_p()
     assert L.pcx_fft_create(pcx.I32, 64, 0, C.byref(f)) == pcx._lib.ERR_ARG      # FFTFactory: unsupported type
