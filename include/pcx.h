@@ -579,6 +579,54 @@ PCX_API int pcx_probe_windows(pcx_probe *h, const void *in, size_t n, double *va
 PCX_API int pcx_probe_windows_dev(pcx_probe *h, const void *in_dev, size_t n, double *values_dev, void *stream);
 
 /* ===================================================================== *
+ *  /comms/wave_trigger      utility/WaveTrigger.cpp
+ *
+ *  The two device parts of the block: the level search (:735-771) and the capture of the windows (:515-582).  The search converts the
+ *  stream to float -- static_cast<float> per component, a complex element to the modulus of its converted components, glibc's hypotf --
+ *  and looks at the pairs (y[i], y[i + 1]): a pair triggers when y0 < level && y1 >= level (POS), y0 > level && y1 <= level (NEG) or
+ *  either (LEVEL), compared in double.  It reports the LEAST triggering i and the pair's two floats; the caller forms the reference's
+ *  position i + (level - y0) / (y1 - y0) from them (a float subtraction, the rest double), see pcx_trigger_position.  The result is a
+ *  minimum: the same from run to run.  Modes, hold-off, windows, labels and messages are the block's (trigger_blocks.cpp).
+ * ===================================================================== */
+typedef struct pcx_trigger pcx_trigger;
+enum { PCX_TRIGGER_POS = 0, PCX_TRIGGER_NEG = 1, PCX_TRIGGER_LEVEL = 2 };
+#define PCX_TRIGGER_MAX_PORTS 16
+/* what a search leaves: 24 bytes.  found is 0 or 1; with 0 the other three are 0 */
+typedef struct pcx_trigger_hit {
+    uint64_t i;
+    float y0, y1;
+    uint64_t found;
+} pcx_trigger_hit;
+/* scalar in {F64, F32, I64, I32, I16, I8}, real or complex, or {U64, U32, U16, U8}, real; anything else is PCX_ERR_ARG.  Level 0.5,
+ * slope POS (:222-224) */
+PCX_API int pcx_trigger_create(pcx_trigger **out, int scalar, int is_complex);
+PCX_API int pcx_trigger_destroy(pcx_trigger *h);
+PCX_API int pcx_trigger_set_level(pcx_trigger *h, double level);
+PCX_API int pcx_trigger_get_level(const pcx_trigger *h, double *level);
+/* PCX_TRIGGER_POS / NEG / LEVEL; any other code is PCX_ERR_ARG */
+PCX_API int pcx_trigger_set_slope(pcx_trigger *h, int slope);
+PCX_API int pcx_trigger_get_slope(const pcx_trigger *h, int *slope);
+/* the pairs a workgroup searches at a time (the seam a test wants to straddle) */
+PCX_API int pcx_trigger_get_geometry(const pcx_trigger *h, size_t *tile);
+/* the least triggering pair i with from <= i <= n - 2 of the n elements at in (none when n < 2 or from > n - 2).  search takes a host
+ * pointer (pageable: staged; page-locked or device memory: searched where it lies) and returns the hit; only the 24 bytes of the
+ * result are read back.  search_dev takes device pointers, leaves the hit in device memory, allocates nothing and synchronises
+ * nothing.  Checked in this order before any device call: the handle, the hit, in. */
+PCX_API int pcx_trigger_search(pcx_trigger *h, const void *in, size_t n, size_t from, pcx_trigger_hit *hit);
+PCX_API int pcx_trigger_search_dev(pcx_trigger *h, const void *in_dev, size_t n, size_t from, pcx_trigger_hit *hit_dev, void *stream);
+/* searchTriggerPointReal's result from a hit (:747): i + (level - y0) / (y1 - y0), y1 - y0 in float, the rest in double */
+PCX_API double pcx_trigger_position(const pcx_trigger_hit *hit, double level);
+/* rows [starts[e], starts[e] + W) of each of nports buffers (elem_bytes[p] bytes per element, any byte address) into outs[p], an
+ * nev x W matrix of the same elements; one launch for all ports, at most PCX_TRIGGER_MAX_PORTS of them.  Every row must lie inside
+ * its buffer: nothing can check that.  capture takes host arrays; a buffer may be pageable (the span of the rows is staged),
+ * page-locked or device memory.  capture_dev takes device pointers throughout (ins_dev, outs_dev: host arrays of device pointers;
+ * starts_dev: a device array), allocates nothing and synchronises nothing. */
+PCX_API int pcx_trigger_capture(pcx_trigger *h, size_t nports, const void *const *ins, const size_t *elem_bytes, const uint64_t *starts, size_t nev, size_t W,
+                                void *const *outs);
+PCX_API int pcx_trigger_capture_dev(pcx_trigger *h, size_t nports, const void *const *ins_dev, const size_t *elem_bytes, const uint64_t *starts_dev, size_t nev,
+                                    size_t W, void *const *outs_dev, void *stream);
+
+/* ===================================================================== *
  *  /comms/preamble_framer      digital/PreambleFramer.cpp
  *  /comms/frame_insert         digital/FrameInsert.cpp, digital/FrameHelper.hpp
  *

@@ -71,6 +71,7 @@ PCXB_API int pcxb_call_string(pcxb_block *b, const char *name, const char *v);
 PCXB_API int pcxb_call_taps(pcxb_block *b, const char *name, const double *taps, size_t n, int is_complex);
 PCXB_API int pcxb_call_sizes(pcxb_block *b, const char *name, const size_t *v, size_t n);   /* std::vector<size_t> (setPreload) */
 PCXB_API int pcxb_get_sizes(pcxb_block *b, const char *name, size_t *out, size_t cap, size_t *n);
+PCXB_API int pcxb_call_strings(pcxb_block *b, const char *name, const char *const *v, size_t n);   /* std::vector<std::string> (setIdsList of /comms/wave_trigger) */
 /* std::vector<unsigned char> (setPreamble / getPreamble of /comms/preamble_correlator); *n = the vector's length, the first min(*n, cap)
  * bytes go to out.  An unsigned argument (setThreshold) travels through pcxb_call_size / pcxb_get_size. */
 PCXB_API int pcxb_call_bytes(pcxb_block *b, const char *name, const unsigned char *v, size_t n);
@@ -155,6 +156,38 @@ PCXB_API int pcxb_port_info(pcxb_block *b, int is_output, size_t i, char *name, 
  * waveform module) is driven through here with nin = 0: ins, in_elems and consumed may then be NULL. */
 PCXB_API int pcxb_work_ports(pcxb_block *b, size_t nin, const void *const *ins, const size_t *in_elems, size_t nout,
                              void *const *outs, const size_t *out_elems, size_t *consumed, size_t *produced);
+
+/*
+ * MESSAGES AND PACKETS (Pothos::InputPort::popMessage, Pothos::OutputPort::postMessage, Pothos::Packet): the surface of
+ * /comms/wave_trigger, whose input ports have no type of their own and whose output carries messages only.
+ *
+ * A port set up without a type counts in BYTES (elements(), consume(), setReserve() and the indices and widths of its labels), as in
+ * Pothos; its buffers carry the type planted here ("" or "unspecified": none, the block drops such a buffer).
+ */
+PCXB_API int pcxb_plant_dtype(pcxb_block *b, size_t port, const char *dtype);
+/* queue a message on input `port`: a Packet (payload bytes copied, of type `dtype` -- "" for a packet without a payload type --, its
+ * labels in elements of the payload, its metadata as records whose id is the key and whose data is the value), or a Label */
+PCXB_API int pcxb_queue_packet(pcxb_block *b, size_t port, const void *payload, size_t bytes, const char *dtype, const pcxb_label *labels,
+                               size_t nlabels, const pcxb_label *metadata, size_t nmetadata);
+PCXB_API int pcxb_queue_label(pcxb_block *b, size_t port, const pcxb_label *label);
+/* One work() call over the indexed input ports: ins[i] holds in_elems[i] elements of the port's type (of the planted type on a port
+ * without one) and carries nlabels[i] labels, all of them in `labels` port after port, in the port's own units.  Output ports get no
+ * buffer.  Then propagateLabels() per port on the labels inside what was consumed.  consumed[i] and reserve[i] are in the port's own
+ * units (reserve: SIZE_MAX if setReserve was not called); *yielded = 1 if work() called yield().  What the block posts stays queued on
+ * its output until pcxb_messages_clear. */
+PCXB_API int pcxb_work_inputs(pcxb_block *b, size_t nin, const void *const *ins, const size_t *in_elems, const pcxb_label *labels,
+                              const size_t *nlabels, size_t *consumed, size_t *reserve, int *yielded);
+/* what output 0 holds, oldest first.  kind: PCXB_MSG_PACKET, PCXB_MSG_LABEL or PCXB_MSG_OTHER.  Of a packet: the payload's type and
+ * bytes, the number of labels, and the metadata "index" (the input port), "position" (the raw double) and "level"; *has is the sum of
+ * PCXB_HAS_INDEX / _POSITION / _LEVEL for the keys present.  Of a label message: nlabels = 1, fetched with pcxb_message_labels. */
+enum { PCXB_MSG_OTHER = 0, PCXB_MSG_PACKET = 1, PCXB_MSG_LABEL = 2 };
+enum { PCXB_HAS_INDEX = 1, PCXB_HAS_POSITION = 2, PCXB_HAS_LEVEL = 4 };
+PCXB_API int pcxb_message_count(pcxb_block *b, size_t *count);
+PCXB_API int pcxb_message_info(pcxb_block *b, size_t i, int *kind, char *dtype, size_t dtype_cap, size_t *bytes, size_t *nlabels, int *has,
+                               int64_t *index, double *position, double *level);
+PCXB_API int pcxb_message_payload(pcxb_block *b, size_t i, void *out, size_t cap);
+PCXB_API int pcxb_message_labels(pcxb_block *b, size_t i, pcxb_label *out, size_t cap);
+PCXB_API int pcxb_messages_clear(pcxb_block *b);
 
 #ifdef __cplusplus
 }

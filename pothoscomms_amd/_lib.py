@@ -45,7 +45,9 @@ WAVE_CONST, WAVE_SINE, WAVE_RAMP, WAVE_SQUARE = 0, 1, 2, 3                      
 NOISE_UNIFORM, NOISE_NORMAL, NOISE_LAPLACE, NOISE_POISSON = 0, 1, 2, 3           # pcx_noise_table
 NOISE_ENTRIES = 4096
 PROBE_VALUE, PROBE_RMS, PROBE_MEAN = 0, 1, 2                                     # pcx_probe_set_mode
-FRAME_OTHER, FRAME_START, FRAME_END = 0, 1, 2                                    # pcx_frame_event.kind
+TRIGGER_POS, TRIGGER_NEG, TRIGGER_LEVEL = 0, 1, 2                                # pcx_trigger_set_slope
+TRIGGER_MAX_PORTS = 16
+FRAME_OTHER, FRAME_START, FRAME_END = 0, 1, 2                                   # pcx_frame_event.kind
 SEG_INPUT, SEG_POOL, SEG_HEADER, SEG_ZERO = 0, 1, 2, 3                           # pcx_frame_segment.kind
 FRAME_HEADER_BITS = 58
 
@@ -111,6 +113,11 @@ class FsyncResult(C.Structure):
     _fields_ = [("consumed", C.c_uint64), ("produced", C.c_uint64), ("reserve", C.c_uint64), ("n_labels", C.c_uint32), ("reserved", C.c_uint32),
                 ("labels", FsyncLabel * 3), ("remaining", C.c_uint64), ("phase", C.c_double), ("phase_inc", C.c_double), ("scale", C.c_double),
                 ("delta_fc", C.c_double), ("phase_off", C.c_double), ("max_peak", C.c_uint64), ("count_since_max", C.c_uint64)]
+
+
+class TriggerHit(C.Structure):
+    """pcx_trigger_hit: what a wave trigger search leaves, 24 bytes."""
+    _fields_ = [("i", C.c_uint64), ("y0", C.c_float), ("y1", C.c_float), ("found", C.c_uint64)]
 
 
 _vp, _sz, _i, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_double
@@ -246,6 +253,18 @@ SIGNATURES = {
     "pcx_probe_process_dev": (_i, [_vp, _vp, _sz, _vp, _psz, _vp]),
     "pcx_probe_windows": (_i, [_vp, _vp, _sz, _vp]),
     "pcx_probe_windows_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "pcx_trigger_create": (_i, [C.POINTER(_vp), _i, _i]),
+    "pcx_trigger_destroy": (_i, [_vp]),
+    "pcx_trigger_set_level": (_i, [_vp, _d]),
+    "pcx_trigger_get_level": (_i, [_vp, C.POINTER(_d)]),
+    "pcx_trigger_set_slope": (_i, [_vp, _i]),
+    "pcx_trigger_get_slope": (_i, [_vp, C.POINTER(_i)]),
+    "pcx_trigger_get_geometry": (_i, [_vp, _psz]),
+    "pcx_trigger_search": (_i, [_vp, _vp, _sz, _sz, C.POINTER(TriggerHit)]),
+    "pcx_trigger_search_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "pcx_trigger_position": (_d, [C.POINTER(TriggerHit), _d]),
+    "pcx_trigger_capture": (_i, [_vp, _sz, C.POINTER(_vp), _psz, _vp, _sz, _sz, C.POINTER(_vp)]),
+    "pcx_trigger_capture_dev": (_i, [_vp, _sz, C.POINTER(_vp), _psz, _vp, _sz, _sz, C.POINTER(_vp), _vp]),
     "pcx_framer_create": (_i, [C.POINTER(_vp), _i, _i]),
     "pcx_framer_destroy": (_i, [_vp]),
     "pcx_framer_set_preamble": (_i, [_vp, _vp, _sz, _sz, _i]),

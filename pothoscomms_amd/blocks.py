@@ -73,7 +73,11 @@ MODULES = {"comms": BLOCKS_LIB_PATH, "filter": os.path.join(_HERE, "libpcx_filte
            "waveform": os.path.join(_HERE, "libpcx_waveform_blocks.so"), "utility": os.path.join(_HERE, "libpcx_utility_blocks.so"),
            "framer": os.path.join(_HERE, "libpcx_framer_blocks.so"), "logic": os.path.join(_HERE, "libpcx_logic_blocks.so"),
            "math": os.path.join(_HERE, "libpcx_math_blocks.so"), "special": os.path.join(_HERE, "libpcx_special_blocks.so"),
-           "probe": os.path.join(_HERE, "libpcx_probe_blocks.so"), "framesync": os.path.join(_HERE, "libpcx_framesync_blocks.so")}
+           "probe": os.path.join(_HERE, "libpcx_probe_blocks.so"), "framesync": os.path.join(_HERE, "libpcx_framesync_blocks.so"),
+           # "trigger" libpcx_trigger_blocks.so (trigger_blocks.cpp: /comms/wave_trigger, input ports without a type, messages on its output)
+           "trigger": os.path.join(_HERE, "libpcx_trigger_blocks.so")}
+MSG_OTHER, MSG_PACKET, MSG_LABEL = 0, 1, 2
+HAS_INDEX, HAS_POSITION, HAS_LEVEL = 1, 2, 4
 _mlibs = {}
 
 
@@ -143,6 +147,17 @@ def load(module="comms"):
     L.pcxb_work_ports.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     L.pcxb_work.argtypes = [vp, vp, sz, C.POINTER(PcxbLabel), sz, vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz),
                             C.POINTER(PcxbLabel), sz, C.POINTER(sz)]
+    L.pcxb_call_strings.argtypes = [vp, cp, C.POINTER(cp), sz]
+    L.pcxb_plant_dtype.argtypes = [vp, sz, cp]
+    L.pcxb_queue_packet.argtypes = [vp, sz, vp, sz, cp, C.POINTER(PcxbLabel), sz, C.POINTER(PcxbLabel), sz]
+    L.pcxb_queue_label.argtypes = [vp, sz, C.POINTER(PcxbLabel)]
+    L.pcxb_work_inputs.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(PcxbLabel), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(i)]
+    L.pcxb_message_count.argtypes = [vp, C.POINTER(sz)]
+    L.pcxb_message_info.argtypes = [vp, sz, C.POINTER(i), cp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(i), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.pcxb_message_payload.argtypes = [vp, sz, vp, sz]
+    L.pcxb_message_labels.argtypes = [vp, sz, C.POINTER(PcxbLabel), sz]
+    L.pcxb_messages_clear.argtypes = [vp]
     if module == "comms":
         _blib = L
     else:
@@ -215,6 +230,18 @@ class Label:
         elif c.kind == STRING:
             data = c.sval.decode()
         return Label(c.id.decode(), c.index, data, c.width)
+
+
+class Message:
+    """a Packet a block posted: the metadata "index", "position" (the raw double) and "level" (None where the key is absent), the
+    payload's type name, its bytes and its labels (indices in elements of the payload)"""
+
+    def __init__(self, index, position, level, dtype, payload, labels):
+        self.index, self.position, self.level, self.dtype, self.payload, self.labels = index, position, level, dtype, payload, labels
+
+    def __repr__(self):
+        return "Message(index=%r, position=%r, level=%r, dtype=%r, %d bytes, %r)" % (self.index, self.position, self.level, self.dtype,
+                                                                                     self.payload.size, self.labels)
 
 
 class Block:
@@ -298,6 +325,21 @@ class Block:
             v, cnt = (C.c_size_t * 64)(), C.c_size_t()
             _check_in(self._module, L.pcxb_get_sizes(self._h, n, v, 64, C.byref(cnt)))
             return [int(v[k]) for k in range(cnt.value)]
+        if name == "setIdsList":                # std::vector<std::string>
+            v = (C.c_char_p * max(1, len(args[0])))(*[str(a).encode() for a in args[0]])
+            return _check_in(self._module, L.pcxb_call_strings(self._h, n, v, len(args[0])))
+        if name in ("getNumPoints", "getNumWindows", "getPosition") and not args:
+            v = C.c_size_t()
+            _check_in(self._module, L.pcxb_get_size(self._h, n, C.byref(v)))
+            return v.value
+        if name in ("getAlignment", "getHoldOff", "getSource") and not args:      # (the last two are bool in the reference, WaveTrigger.cpp:273, :284)
+            v = C.c_int()
+            _check_in(self._module, L.pcxb_get_bool(self._h, n, C.byref(v)))
+            return bool(v.value)
+        if name in ("getEventRate", "getLevel") and not args:
+            v = C.c_double()
+            _check_in(self._module, L.pcxb_get_double(self._h, n, C.byref(v)))
+            return v.value
         if name in ("setPoly", "setSeed"):      # int64_t, negative values included
             v = int(args[0])
             return _check_in(self._module, L.pcxb_call_int64(self._h, n, v - (1 << 64) if v >= (1 << 63) else v))
@@ -520,6 +562,75 @@ class Block:
         cons, prod = (C.c_size_t * len(in_ptrs))(), (C.c_size_t * len(out_ptrs))()
         _check_in(self._module, load(self._module).pcxb_work_ports(self._h, len(in_ptrs), ins, nin, len(out_ptrs), outs, nout, cons, prod))
         return [int(v) for v in cons], [int(v) for v in prod]
+
+    # ---- messages and packets (/comms/wave_trigger) ----
+    def plant_dtype(self, port, dtype):
+        """the type the buffers planted on input `port` carry, for a port that has none of its own ("" or None: unspecified)"""
+        _check_in(self._module, load(self._module).pcxb_plant_dtype(self._h, port, (dtype or "").encode()))
+
+    @staticmethod
+    def _labels_to_c(labels):
+        labs = (PcxbLabel * max(1, len(labels)))()
+        for i, l in enumerate(labels):
+            l._to_c(labs[i])
+        return labs
+
+    def queue_packet(self, port, payload, dtype, labels=(), metadata=None):
+        """a Packet on input `port`: payload a numpy array (its bytes are copied), dtype the payload's type name ("" or None: none),
+        labels in elements of the payload, metadata {key: int, float or str}"""
+        raw = np.ascontiguousarray(payload).view(np.uint8).reshape(-1)
+        meta = [Label(k, 0, v) for k, v in (metadata or {}).items()]
+        _check_in(self._module, load(self._module).pcxb_queue_packet(self._h, port, raw.ctypes.data_as(C.c_void_p) if raw.size else None, raw.size,
+                                                                     (dtype or "").encode(), self._labels_to_c(labels), len(labels),
+                                                                     self._labels_to_c(meta), len(meta)))
+
+    def queue_label(self, port, label):
+        """a Label as a message on input `port`"""
+        _check_in(self._module, load(self._module).pcxb_queue_label(self._h, port, self._labels_to_c([label])))
+
+    def work_inputs(self, in_ptrs, in_elems, labels=None):
+        """One work() call over the indexed input ports on raw buffer addresses (host or device memory): in_elems[i] elements of port
+        i's type (of the planted type on a port without one), labels[i] the port's labels in the port's own units (bytes on a port
+        without a type).  Returns (consumed, reserve, yielded): per port, in the port's own units, reserve None where none was asked
+        for.  What the block posted stays queued: messages()."""
+        nin = len(in_ptrs)
+        labels = labels or [()] * nin
+        flat = [l for port in labels for l in port]
+        ins, ne = (C.c_void_p * max(1, nin))(*in_ptrs), (C.c_size_t * max(1, nin))(*in_elems)
+        nl = (C.c_size_t * max(1, nin))(*[len(p) for p in labels])
+        cons, res, y = (C.c_size_t * max(1, nin))(), (C.c_size_t * max(1, nin))(), C.c_int()
+        _check_in(self._module, load(self._module).pcxb_work_inputs(self._h, nin, ins, ne, self._labels_to_c(flat), nl, cons, res, C.byref(y)))
+        return [int(v) for v in cons][:nin], [None if v == _SIZE_MAX else int(v) for v in res][:nin], bool(y.value)
+
+    def messages(self, clear=True):
+        """what output 0 holds, oldest first: ("packet", Message) / ("label", Label) / ("other", None).  A Message has index (the
+        metadata "index", or None), position (the raw double, or None), level, dtype, payload (uint8) and labels."""
+        L = load(self._module)
+        n = C.c_size_t()
+        _check_in(self._module, L.pcxb_message_count(self._h, C.byref(n)))
+        out = []
+        for k in range(n.value):
+            kind, dt, nb, nl, has = C.c_int(), C.create_string_buffer(64), C.c_size_t(), C.c_size_t(), C.c_int()
+            idx, pos, lev = C.c_int64(), C.c_double(), C.c_double()
+            _check_in(self._module, L.pcxb_message_info(self._h, k, C.byref(kind), dt, 64, C.byref(nb), C.byref(nl), C.byref(has), C.byref(idx),
+                                                        C.byref(pos), C.byref(lev)))
+            labs = (PcxbLabel * max(1, nl.value))()
+            if kind.value != MSG_OTHER:
+                _check_in(self._module, L.pcxb_message_labels(self._h, k, labs, nl.value))
+            labels = [Label._from_c(labs[j]) for j in range(nl.value)]
+            if kind.value == MSG_LABEL:
+                out.append(("label", labels[0]))
+            elif kind.value == MSG_PACKET:
+                payload = np.zeros(nb.value, np.uint8)
+                if nb.value:
+                    _check_in(self._module, L.pcxb_message_payload(self._h, k, payload.ctypes.data_as(C.c_void_p), nb.value))
+                out.append(("packet", Message(idx.value if has.value & HAS_INDEX else None, pos.value if has.value & HAS_POSITION else None,
+                                              lev.value if has.value & HAS_LEVEL else None, dt.value.decode(), payload, labels)))
+            else:
+                out.append(("other", None))
+        if clear:
+            _check_in(self._module, L.pcxb_messages_clear(self._h))
+        return out
 
     def work(self, inbuf, out_elems, labels=(), outbuf=None, label_cap=64):
         """One work() call.  Returns (out[:produced], consumed, produced, reserve, posted_labels).

@@ -4,7 +4,9 @@
 // reference files use (Block::{setupInput,setupOutput,registerCall,input,output,
 // workInfo}, InputPort::{elements,buffer,labels,setReserve,consume,dtype}, OutputPort::{elements,
 // buffer,produce,postLabel}, BufferChunk, Label, Object, DType, BufferManager, BlockRegistry,
-// InvalidArgumentException).
+// InvalidArgumentException), and what utility/WaveTrigger.cpp adds to it: messages and packets (Packet, InputPort::{hasMessage,popMessage,
+// takeBuffer}, OutputPort::postMessage, Object holding a Packet or a Label, BufferChunk::{getEnd,operator bool}, Label::adjust,
+// Block::yield) and input ports without a type, which count in bytes and whose buffers carry the type they were planted with.
 //
 //   -DPCX_WITH_POTHOS : `namespace pcxfw` IS Pothos (<Pothos/Framework.hpp>): the same block
 //                       sources build into a Pothos plugin module.
@@ -76,6 +78,8 @@ public:
     bool isInteger() const { return _name.find("int") != std::string::npos; }
     bool operator==(const DType &o) const { return _name == o._name && _dim == o._dim; }
     bool operator!=(const DType &o) const { return !(*this == o); }
+    // Pothos::DType: false for the unspecified type (what a port set up without a type has, utility/WaveTrigger.cpp:187, :490, :500)
+    explicit operator bool() const { return _name != "unspecified"; }
 
 private:
     static std::string nameOf(const std::type_info &t)
@@ -109,7 +113,9 @@ private:
     size_t _elemSize, _dim;
 };
 
-// ---- Object: a small type-erased value (numbers, strings, tap vectors, DType) ----
+// ---- Object: a small type-erased value (numbers, strings, tap vectors, DType; a Packet or a Label travelling as a message) ----
+struct Packet;
+struct Label;
 class Object {
 public:
     Object() : _t(&typeid(void)) {}
@@ -133,6 +139,18 @@ public:
     Object(const std::vector<std::complex<double>> &v) : _t(&typeid(std::vector<std::complex<double>>)), _vc(v) {}
     Object(const std::vector<size_t> &v) : _t(&typeid(std::vector<size_t>)), _vs(v) {}
     Object(const std::vector<unsigned char> &v) : _t(&typeid(std::vector<unsigned char>)), _vb(v) {}     // digital/PreambleCorrelator.cpp:77
+    Object(const std::vector<std::string> &v) : _t(&typeid(std::vector<std::string>)), _boxed(std::make_shared<std::vector<std::string>>(v)) {}     // utility/WaveTrigger.cpp:381
+
+    // a message (InputPort::popMessage / OutputPort::postMessage): a Packet or a Label, held by value behind a shared pointer
+    Object(const Packet &p);
+    Object(const Label &l);
+    // Pothos::Object::extract<T>(): the held Packet or Label itself, no conversion
+    template <typename T>
+    const T &extract() const
+    {
+        if (*_t != typeid(T) || !_boxed) throw Exception("Object::extract()", std::string("the object holds ") + _t->name());
+        return *static_cast<const T *>(_boxed.get());
+    }
 
     const std::type_info &type() const { return *_t; }
     bool isNumber() const
@@ -208,6 +226,7 @@ private:
         return _vs;
     }
     std::vector<unsigned char> get(std::vector<unsigned char> *) const { return _vb; }
+    std::vector<std::string> get(std::vector<std::string> *) const { return *static_cast<const std::vector<std::string> *>(_boxed.get()); }
     const std::type_info *_t;
     double _d = 0, _im = 0;
     long long _i = 0;
@@ -216,6 +235,7 @@ private:
     std::vector<std::complex<double>> _vc;
     std::vector<size_t> _vs;
     std::vector<unsigned char> _vb;
+    std::shared_ptr<const void> _boxed;
 };
 
 // ---- BufferChunk: a view (optionally owning) of typed memory ----
@@ -240,11 +260,22 @@ public:
         b.dtype = dt;
         return b;
     }
+    // extension: a chunk that owns memory of another allocator (page-locked memory of pcx_host_alloc): `release` runs when the last
+    // copy of the chunk goes.  In a Pothos build the same is a BufferChunk over a SharedBuffer with a container.
+    static BufferChunk adopt(void *p, size_t bytes, const DType &dt, void (*release)(void *))
+    {
+        BufferChunk b = view(p, bytes, dt);
+        b._own.reset(static_cast<char *>(p), [release](char *q) { release(q); });
+        return b;
+    }
     size_t elements() const { return length / dtype.size(); }
     template <typename T>
     T as() const { return reinterpret_cast<T>(address); }
     template <typename T>
     operator T *() const { return reinterpret_cast<T *>(address); }
+    // Pothos::BufferChunk::getEnd(): the address behind the last byte; operator bool: is there memory behind the chunk
+    size_t getEnd() const { return address + length; }
+    explicit operator bool() const { return address != 0; }
 
 private:
     std::shared_ptr<char> _own;
@@ -266,7 +297,23 @@ struct Label {
         l.width = l.width * mult / div;
         return l;
     }
+    // Pothos::Label::adjust: the same, in place
+    Label &adjust(size_t mult, size_t div)
+    {
+        index = index * mult / div;
+        width = width * mult / div;
+        return *this;
+    }
 };
+
+// ---- Packet: a payload with its metadata and the labels that lie on it (indices in elements of the payload) ----
+struct Packet {
+    BufferChunk payload;
+    std::map<std::string, Object> metadata;
+    std::vector<Label> labels;
+};
+inline Object::Object(const Packet &p) : _t(&typeid(Packet)), _boxed(std::make_shared<Packet>(p)) {}
+inline Object::Object(const Label &l) : _t(&typeid(Label)), _boxed(std::make_shared<Label>(l)) {}
 
 struct WorkInfo {
     // minElements: over the indexed ports; minAllElements: indexed and named ports alike
@@ -347,8 +394,20 @@ class Block;
 class InputPort {
 public:
     const BufferChunk &buffer() const { return _buffer; }
-    size_t elements() const { return _buffer.elements(); }
+    // in units of the PORT's type: bytes on a port set up without one, whose buffers carry the type they were planted with
+    size_t elements() const { return _buffer.length / _dtype.size(); }
     const std::vector<Label> &labels() const { return _labels; }
+    // messages (Pothos::InputPort): what upstream posted, in order of arrival
+    bool hasMessage() const { return !_messages.empty(); }
+    Object popMessage()
+    {
+        if (_messages.empty()) return Object();
+        Object m = _messages.front();
+        _messages.erase(_messages.begin());
+        return m;
+    }
+    // Pothos::InputPort::takeBuffer(): the port's buffer for keeping (a view here: the planted memory belongs to the scheduler's side)
+    BufferChunk takeBuffer() const { return _buffer; }
     void consume(size_t n) { _consumed += n; }
     void setReserve(size_t n) { _reserve = n; _reserveSet = true; }
     const DType &dtype() const { return _dtype; }
@@ -368,6 +427,8 @@ public:
     int _index = -1;
     std::string _name;
     std::vector<BufferChunk> _pushed;
+    std::vector<Object> _messages;
+    DType _plantedDtype;                   // what the scheduler's side plants on a port without a type of its own
 };
 class OutputPort {
 public:
@@ -375,6 +436,8 @@ public:
     size_t elements() const { return _buffer.elements(); }
     void produce(size_t n) { _produced += n; }
     void postLabel(const Label &l) { _posted.push_back(l); }
+    // Pothos::OutputPort::postMessage: a Packet, a Label or any other Object for the downstream port's message queue
+    void postMessage(const Object &m) { _messages.push_back(m); }
     const DType &dtype() const { return _dtype; }
     const std::string &domain() const { return _domain; }
     std::string _domain;
@@ -389,6 +452,7 @@ public:
     int _index = -1;
     std::string _name;
     InputPort *_readBeforeWrite = nullptr;
+    std::vector<Object> _messages;
 };
 
 // ---- registered calls: name -> type-erased member function ----
@@ -567,6 +631,9 @@ public:
     // true from just before activate() until deactivate() returns, as the Pothos actor keeps it
     bool isActive() const { return _active; }
     void setActiveState(bool on) { _active = on; }
+    // Pothos::Block::yield(): work() wants to be called again without new input; the scheduler's side reads and clears the flag
+    void yield() { _yielded = true; }
+    bool takeYield() { const bool y = _yielded; _yielded = false; return y; }
 
 private:
     std::vector<std::unique_ptr<InputPort>> _inputs, _namedInputs;
@@ -578,6 +645,7 @@ private:
     std::map<std::string, size_t> _callArity;
     std::map<std::string, std::vector<std::pair<Block *, std::string>>> _signals;
     bool _active = false;
+    bool _yielded = false;
 };
 
 #define PCX_FCN_TUPLE(c, m) #m, &c::m

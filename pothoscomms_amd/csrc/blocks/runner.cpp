@@ -176,6 +176,10 @@ int pcxb_get_sizes(pcxb_block *b, const char *name, size_t *out, size_t cap, siz
         for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
     });
 }
+int pcxb_call_strings(pcxb_block *b, const char *name, const char *const *v, size_t n)
+{
+    return guarded([&] { b->blk->call(name, {Object(std::vector<std::string>(v, v + n))}); });
+}
 int pcxb_call_bytes(pcxb_block *b, const char *name, const unsigned char *v, size_t n)
 {
     return guarded([&] { b->blk->call(name, {Object(n ? std::vector<unsigned char>(v, v + n) : std::vector<unsigned char>())}); });
@@ -436,5 +440,122 @@ int pcxb_work_ports(pcxb_block *b, size_t nin, const void *const *ins, const siz
         for (size_t i = 0; i < nout; i++) produced[i] = ops[i]->_produced;
     });
 }
+
+// ---- messages and packets ----
+static DType plantedType(const char *dtype)
+{
+    const std::string n(dtype ? dtype : "");
+    return n.empty() || n == "unspecified" ? DType() : DType(n);
+}
+static const Object &messageAt(pcxb_block *b, size_t i)
+{
+    const auto &m = b->blk->output(0)->_messages;
+    if (i >= m.size()) throw pcxfw::Exception("pcxb_message()", "index out of range");
+    return m[i];
+}
+int pcxb_plant_dtype(pcxb_block *b, size_t port, const char *dtype)
+{
+    return guarded([&] { b->blk->input(port)->_plantedDtype = plantedType(dtype); });
+}
+int pcxb_queue_packet(pcxb_block *b, size_t port, const void *payload, size_t bytes, const char *dtype, const pcxb_label *labels, size_t nlabels,
+                      const pcxb_label *metadata, size_t nmetadata)
+{
+    return guarded([&] {
+        Packet pkt;
+        const DType dt = plantedType(dtype);
+        pkt.payload = BufferChunk(DType("uint8"), bytes);
+        if (bytes) std::memcpy(pkt.payload.as<void *>(), payload, bytes);
+        pkt.payload.dtype = dt;
+        for (size_t i = 0; i < nlabels; i++) pkt.labels.push_back(toLabel(labels[i]));
+        for (size_t i = 0; i < nmetadata; i++) pkt.metadata[metadata[i].id] = toLabel(metadata[i]).data;
+        b->blk->input(port)->_messages.push_back(Object(pkt));
+    });
+}
+int pcxb_queue_label(pcxb_block *b, size_t port, const pcxb_label *label)
+{
+    return guarded([&] { b->blk->input(port)->_messages.push_back(Object(toLabel(*label))); });
+}
+int pcxb_work_inputs(pcxb_block *b, size_t nin, const void *const *ins, const size_t *in_elems, const pcxb_label *labels, const size_t *nlabels,
+                     size_t *consumed, size_t *reserve, int *yielded)
+{
+    return guarded([&] {
+        const auto ips = b->blk->inputs();
+        if (ips.size() != nin) throw pcxfw::Exception("pcxb_work_inputs()", "port count mismatch");
+        const size_t none = std::numeric_limits<size_t>::max();
+        size_t minIn = none, at = 0;
+        for (size_t i = 0; i < nin; i++) {
+            InputPort *ip = ips[i];
+            const DType dt = ip->dtype() ? ip->dtype() : ip->_plantedDtype;
+            ip->_buffer = BufferChunk::view(const_cast<void *>(ins[i]), in_elems[i] * dt.size(), dt);
+            ip->_labels.clear();
+            for (size_t k = 0; k < nlabels[i]; k++) ip->_labels.push_back(toLabel(labels[at + k]));
+            at += nlabels[i];
+            ip->_consumed = 0; ip->_reserveSet = false; ip->_reserve = 0;
+            minIn = std::min(minIn, ip->elements());
+        }
+        for (OutputPort *op : b->blk->outputs()) {
+            op->_buffer = BufferChunk();
+            op->_produced = 0; op->_posted.clear();
+        }
+        WorkInfo &wi = b->blk->workInfoMutable();
+        wi.minInElements = minIn == none ? 0 : minIn;
+        wi.minOutElements = 0;
+        wi.minElements = wi.minAllElements = 0;
+        (void)b->blk->takeYield();
+        b->blk->work();
+        for (size_t i = 0; i < nin; i++) {
+            InputPort *ip = ips[i];
+            consumed[i] = ip->_consumed;
+            reserve[i] = ip->_reserveSet ? ip->_reserve : none;
+            std::vector<Label> inside;
+            for (const auto &l : ip->_labels) if (l.index < ip->_consumed) inside.push_back(l);
+            ip->_labels.swap(inside);
+            if (!ip->_labels.empty()) b->blk->propagateLabels(ip);
+        }
+        if (yielded) *yielded = b->blk->takeYield() ? 1 : 0;
+    });
+}
+int pcxb_message_count(pcxb_block *b, size_t *count) { return guarded([&] { *count = b->blk->output(0)->_messages.size(); }); }
+int pcxb_message_info(pcxb_block *b, size_t i, int *kind, char *dtype, size_t dtype_cap, size_t *bytes, size_t *nlabels, int *has, int64_t *index,
+                      double *position, double *level)
+{
+    return guarded([&] {
+        const Object &m = messageAt(b, i);
+        *kind = PCXB_MSG_OTHER; *bytes = 0; *nlabels = 0; *has = 0; *index = 0; *position = 0.0; *level = 0.0;
+        if (dtype && dtype_cap) dtype[0] = 0;
+        if (m.type() == typeid(Label)) { *kind = PCXB_MSG_LABEL; *nlabels = 1; return; }
+        if (m.type() != typeid(Packet)) return;
+        const Packet &p = m.extract<Packet>();
+        *kind = PCXB_MSG_PACKET;
+        if (dtype) std::snprintf(dtype, dtype_cap, "%s", p.payload.dtype.name().c_str());
+        *bytes = p.payload.length;
+        *nlabels = p.labels.size();
+        auto it = p.metadata.find("index");
+        if (it != p.metadata.end()) { *has |= PCXB_HAS_INDEX; *index = (int64_t)it->second.convert<long long>(); }
+        if ((it = p.metadata.find("position")) != p.metadata.end()) { *has |= PCXB_HAS_POSITION; *position = it->second.convert<double>(); }
+        if ((it = p.metadata.find("level")) != p.metadata.end()) { *has |= PCXB_HAS_LEVEL; *level = it->second.convert<double>(); }
+    });
+}
+int pcxb_message_payload(pcxb_block *b, size_t i, void *out, size_t cap)
+{
+    return guarded([&] {
+        const Packet &p = messageAt(b, i).extract<Packet>();
+        if (p.payload.length > cap) throw InvalidArgumentException("pcxb_message_payload()", "the payload exceeds cap");
+        if (p.payload.length) std::memcpy(out, p.payload.as<const void *>(), p.payload.length);
+    });
+}
+int pcxb_message_labels(pcxb_block *b, size_t i, pcxb_label *out, size_t cap)
+{
+    return guarded([&] {
+        const Object &m = messageAt(b, i);
+        if (m.type() == typeid(Label)) {
+            if (cap) fromLabel(m.extract<Label>(), out[0]);
+            return;
+        }
+        const Packet &p = m.extract<Packet>();
+        for (size_t k = 0; k < p.labels.size() && k < cap; k++) fromLabel(p.labels[k], out[k]);
+    });
+}
+int pcxb_messages_clear(pcxb_block *b) { return guarded([&] { b->blk->output(0)->_messages.clear(); }); }
 
 }  // extern "C"

@@ -348,6 +348,12 @@ size_t probe_max_slices();                  // partials the scratch of a handle 
 // ceil(n / W) windows of the n elements at `in`, the last one the remainder: values receives a pair (re, im) per window.  mode:
 // PCX_PROBE_VALUE / RMS / MEAN.  part: probe_max_slices() pairs of scratch, used when W exceeds probe_tile()
 int launch_probe_windows(int scalar, bool cplx, int mode, const void *in, size_t n, size_t W, double *values, double *part, hipStream_t st);
+// (trigger.hip) /comms/wave_trigger: the least triggering pair of in[from .. n - 2] -- result receives 24 bytes (uint64 i, float y0, float
+// y1, uint64 found), best is one 64-bit word of scratch -- and the capture of nev rows of W elements from each of nports buffers
+size_t trigger_tile();                      // pairs a workgroup searches at a time
+int launch_trigger_search(int scalar, bool cplx, const void *in, size_t n, size_t from, double level, int slope, uint64_t *best, void *result, hipStream_t st);
+int launch_trigger_capture(size_t nports, const void *const *ins, const size_t *elem_bytes, const uint64_t *starts, size_t nev, size_t W, void *const *outs,
+                           hipStream_t st);
 // (splice.hip) /comms/preamble_framer, /comms/frame_insert: one entry of the segment table as the kernel reads it
 struct SpliceSeg {
     uint64_t dst;                           // first output byte

@@ -787,6 +787,99 @@ class SignalProbe(_Handle):
         _lib.check(_lib.load().pcx_probe_windows_dev(self._h, _any_dev_ptr(x), n, _any_dev_ptr(values), _stream_ptr(stream)))
 
 
+class Trigger(_Handle):
+    """pcx_trigger_*: the two device parts of utility/WaveTrigger.cpp -- the least pair (y[i], y[i + 1]) of the stream converted to
+    float (a complex element to its modulus) that crosses `level` with the wanted slope, and the capture of windows of W elements from
+    several buffers at once.  search returns (i, y0, y1, position) or None, position being the reference's
+    i + (level - y0) / (y1 - y0)."""
+    _destroy = "pcx_trigger_destroy"
+    SLOPES = {"POS": _lib.TRIGGER_POS, "NEG": _lib.TRIGGER_NEG, "LEVEL": _lib.TRIGGER_LEVEL}
+
+    def __init__(self, dtype="float32", level=0.5, slope="POS"):
+        super().__init__()
+        self.dtype = dtype
+        self.scalar, self.is_complex = parse_dtype(dtype)
+        _lib.check(_lib.load().pcx_trigger_create(C.byref(self._h), self.scalar, int(self.is_complex)))
+        self.np_dtype = np.dtype(NP_SCALAR[self.scalar])
+        self.elem_bytes = self.np_dtype.itemsize * (2 if self.is_complex else 1)
+        self.set_level(level)
+        self.set_slope(slope)
+
+    def set_level(self, level):
+        _lib.check(_lib.load().pcx_trigger_set_level(self._h, float(level)))
+
+    @property
+    def level(self):
+        v = C.c_double()
+        _lib.check(_lib.load().pcx_trigger_get_level(self._h, C.byref(v)))
+        return v.value
+
+    def set_slope(self, slope):
+        if slope not in self.SLOPES:
+            raise _lib.InvalidArgument(_lib.ERR_ARG, "wave trigger: unknown slope setting %r" % (slope,))
+        _lib.check(_lib.load().pcx_trigger_set_slope(self._h, self.SLOPES[slope]))
+
+    @property
+    def slope(self):
+        v = C.c_int()
+        _lib.check(_lib.load().pcx_trigger_get_slope(self._h, C.byref(v)))
+        return [k for k, c in self.SLOPES.items() if c == v.value][0]
+
+    def geometry(self):
+        """the pairs a workgroup searches at a time"""
+        v = C.c_size_t()
+        _lib.check(_lib.load().pcx_trigger_get_geometry(self._h, C.byref(v)))
+        return v.value
+
+    def _hit(self, hit):
+        if not hit.found:
+            return None
+        return int(hit.i), float(hit.y0), float(hit.y1), float(_lib.load().pcx_trigger_position(C.byref(hit), self.level))
+
+    def search(self, x, start=0, n=None):
+        """x: a numpy array of the element type ((n, 2) or complex for a complex type), or a raw address (host or device memory) with
+        n elements behind it -> the first triggering pair at or behind `start`"""
+        hit = _lib.TriggerHit()
+        if isinstance(x, int):
+            ptr = C.c_void_p(x)
+        else:
+            x = as_pairs(x)
+            if x.dtype != self.np_dtype:
+                raise _lib.InvalidArgument(_lib.ERR_ARG, "wave trigger: %s input for a %s trigger" % (x.dtype, self.dtype))
+            ptr, n = _np_ptr(x), x.shape[0]
+        _lib.check(_lib.load().pcx_trigger_search(self._h, ptr, int(n), int(start), C.byref(hit)))
+        return self._hit(hit)
+
+    def search_dev(self, x, n, start, hit, stream=None):
+        """device tensors (or raw device addresses): n elements at x, hit 24 bytes that receive (uint64 i, float y0, float y1, uint64
+        found); nothing is allocated or synchronised"""
+        _lib.check(_lib.load().pcx_trigger_search_dev(self._h, _any_dev_ptr(x), n, int(start), _any_dev_ptr(hit), _stream_ptr(stream)))
+
+    @staticmethod
+    def _ports(ptrs):
+        return (C.c_void_p * len(ptrs))(*[p if isinstance(p, int) else p.ctypes.data for p in ptrs])
+
+    def capture(self, ins, elem_bytes, starts, W, outs=None):
+        """rows [starts[e], starts[e] + W) of every buffer of `ins` (numpy uint8 arrays or raw addresses, host or device memory;
+        elem_bytes[p] bytes per element) -> one (nev, W * elem_bytes[p]) uint8 matrix per buffer (or into `outs`: raw addresses)"""
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        nev = starts.shape[0]
+        made = None
+        if outs is None:
+            made = [np.zeros((nev, W * eb), np.uint8) for eb in elem_bytes]
+            outs = made
+        eb = (C.c_size_t * len(ins))(*[int(e) for e in elem_bytes])
+        _lib.check(_lib.load().pcx_trigger_capture(self._h, len(ins), self._ports(ins), eb, _np_ptr(starts), nev, int(W), self._ports(outs)))
+        return made
+
+    def capture_dev(self, ins, elem_bytes, starts, nev, W, outs, stream=None):
+        """raw device addresses or device tensors throughout; starts: nev uint64 in device memory; nothing is allocated or synchronised"""
+        addr = lambda v: [p if isinstance(p, int) else p.data_ptr() for p in v]
+        eb = (C.c_size_t * len(ins))(*[int(e) for e in elem_bytes])
+        _lib.check(_lib.load().pcx_trigger_capture_dev(self._h, len(ins), self._ports(addr(ins)), eb, _any_dev_ptr(starts), nev, int(W),
+                                                       self._ports(addr(outs)), _stream_ptr(stream)))
+
+
 class Framer(_Handle):
     """pcx_framer_*: digital/PreambleFramer.cpp (uint8) and digital/FrameInsert.cpp (complex_float32, complex_float64) -- a preamble in
     front of every start label, zero padding behind every end label, the labels of a call given as events (index, width, kind,
