@@ -1,8 +1,9 @@
 // pcx_fir_api.hip -- the extern "C" boundary (include/pcx.h), part 2: /comms/fir_filter (pcx_fir_*) and the fused
 // Rotate -> FIR -> FreqDemod chain (pcx_fmchain_*): tap bookkeeping (FIRFilter.cpp:138-173,327-354), the coefficient tables of
-// every plan, the choice of kernel family per call, host-buffer calls.  Host-side only.
+// the handle's plan (fir_plan.hpp chooses it), host-buffer calls.  Host-side only.
 #include "pcx_host.hpp"
 #include "pcx_tables.hpp"
+#include "fir_plan.hpp"
 
 using namespace pcx;
 
@@ -17,72 +18,23 @@ struct pcx_fir {
     int algo = PCX_FIR_AUTO, last_algo = 0, last_plan = PCX_FIR_PLAN_NONE;
     QFormat qf = kDefaultQFormat;   // integer element types: the floatToQ / fromQ reading (pcx_fir_set_qformat; the process-wide one at creation)
     bool dirty = true;
-    DevBuf rowLen, rowTaps, tapsRev, Hspec, tw4096;
+    FirPlan plan;             // which plan serves these settings (fir_plan.hpp), set with the tables: valid while !dirty
+    DevBuf rowLen, rowTaps, tapsRev;   // the time-domain kernels' tables
+    // the frequency-domain plan's tables: Hspec one spectrum (or the partitions' spectra) of the whole tap vector, HspecRows / HrowsD one
+    // per polyphase row in float / double, Hdecim the lane-ordered spectrum of the folded (CF32_DECIM) and replicated (CF32_INTERP) forms
+    DevBuf Hspec, HspecRows, HrowsD, Hdecim, tw4096;
     StageBuf wsIn, wsOut;
+    DevBuf wsRows;            // the row plans: one contiguous output row per polyphase row, interleaved afterwards
     DevBuf sched;             // SchedState: dynamic block assignment of the overlap-save kernels (pcx_sched.hpp), zeroed once
     unsigned slots = 1024;    // resident workgroups a persistent launch may take (pcx_shard: several shards on one device share it)
     size_t lead_valid = 0;    // set around the chunks of a drained host call: samples of the same stream in front of the chunk's first
     size_t Kp = 8;
-    bool have_ols = false;
-    bool have_poly = false;   // frequency-domain rows for L > 1 or M > 1
-    DevBuf wsRows;            // interpolation by other factors: one contiguous output row per polyphase row, interleaved afterwards
-    bool have_decim = false;  // L = 1, M in {2,4,8,16}: decimation folded into the spectrum (Hdecim)
-    bool have_interp = false; // M = 1, L in {2,4,8,16}: replicated spectrum of the short forward transform (Hdecim holds H of all taps)
-    DevBuf Hdecim;
-    bool have_real_ols = false;   // real float32 stream, real taps, M=L=1
-    bool have_interp_f32 = false;  // REAL float32, L > 1, rows of up to 2049 taps: the real float kernel row by row + interleave
-    bool have_upols_rows = false;  // complex_float32 / float32, L > 1, polyphase rows of 2050 .. 8193 taps: the partitioned kernel row by row + interleave
-    bool have_upols_decim = false; // complex_float32 / float32, L = 1, M > 1, 2049 < K <= 8193: the partitioned kernel with a decimating store
-    bool have_ols64 = false;      // complex_float64 stream, M=L=1 (Hspec / tw4096 then hold doubles)
-    bool have_ols_int = false;    // complex_int16 / complex_int8 stream, M=L=1: exact integer convolution on the double transform
-    bool have_ols_real64 = false; // REAL float64 / int16 / int8 stream (real taps), M=L=1: two real blocks per double transform
-    bool have_interp64 = false;   // complex_float64 / int16 / int8, M = 1, L > 1: polyphase rows on the double pipeline (HrowsD) + interleave
-    bool have_interp_real = false; // REAL float64 / float32 / int16 / int8, L > 1: the same with the two-real-blocks kernel
-    DevBuf HrowsD;
-    DevBuf HspecRows;
-    int ols_parts = 0;        // complex_float32 / float32, M = L = 1: 0 = fir_ols.hip's 4096 kernels alone, 2 .. 4 = that many tap partitions (fir_ols_part.hip)
-    int ols_log2n = 0;        // the double-precision plans: log2 of the block (12, 13)
     bool taps24 = false;      // integer Q taps all fit 24 signed bits (v_mul_i32_i24 path)
     bool taps16 = false;      // complex_int16 / complex_int8 stream, complex taps within +-32767 after floatToQ (v_dot2_i32_i16 path)
     DevBuf tapsP;             // packed (a, -b), (b, a) pairs for that path
 };
 
-// Tap partitions of the overlap-save plan for K taps (complex_float32, M = L = 1): 0 = the dedicated 4096-sample kernel alone
-// (fir_ols.hip, K <= 2049); P = 2 .. 4 = the same blocks with the taps in P partitions of 2048 (fir_ols_part.hip, 2049 < K <= 8193).
-// (Until round 6 longer filters took 8192- / 16384-sample blocks on radix-16 family passes -- 143 / 88 Gsamples/s at 4097 / 8193
-// taps against 206 / 167 now, profiles/r06/ab_upols.txt; blocks SHORTER than 4096 never paid either: 0.2413 ms at 2048, 0.2723 at
-// 1024 against 0.2246 at 255 taps, round 2.)
-static int fir_ols_partitions(size_t K) { return K <= 2049 ? 0 : (int)((K - 1 + 2047) / 2048); }
-constexpr size_t kOlsMaxTaps = 8193;
 constexpr size_t kRowsWorkspaceCap = (size_t)1 << 30;   // polyphase-row workspace of the interpolating paths (pcx_fir_process_dev)
-// complex_float64 (fir_ols_f64.hip): 4096-sample blocks to K = 2049, 8192 to K = 4097; PCX_OLS64_N forces a plan (A/B)
-constexpr size_t kOls64MaxTaps = 4097;
-// below this many taps the sliding-window kernel is the faster complex_float64 form (tools/sweep_fir_f64.py: 128 vs 112 Gsamples/s at K = 2)
-constexpr size_t kOls64MinTaps = 4;
-// complex_int16 / complex_int8 on the same pipeline (bit-exact): 166-170 / 128-131 Gsamples/s whatever the tap count, so it
-// takes over where the packed dot-product kernel falls below that (tools/sweep_fir_int.py: 164 Gsamples/s at 63 taps, 91 at
-// 127, 48 at 255, 12 at 1023); PCX_OLS_INT_MIN overrides (A/B)
-static size_t ols_int_min_taps(int scalar)
-{
-    const size_t forced = (size_t)PCX_ENV_INT("PCX_OLS_INT_MIN", 0);
-    return forced ? forced : scalar == PCX_I16 ? 64 : 96;
-}
-
-// REAL float64 / int16 / int8 streams on the double pipeline, two real blocks per transform: 234 / 290 / 296 Gsamples/s
-// whatever the tap count; the sliding-window kernel is faster below about 24 / 48 / 48 taps (tools/sweep_fir_int.py real:
-// float64 278 vs 228 at 16 taps, 202 vs 234 at 32; int16 356 vs 280 at 32, 230 vs 286 at 63); PCX_OLS_REAL_MIN overrides (A/B)
-static size_t ols_real64_min_taps(int scalar)
-{
-    const size_t forced = (size_t)PCX_ENV_INT("PCX_OLS_REAL_MIN", 0);
-    return forced ? forced : scalar == PCX_F64 ? 24 : 48;
-}
-static int fir_ols64_block_log2(size_t K)
-{
-    const int forced = (int)PCX_ENV_INT("PCX_OLS64_N", 0);
-    int l2 = K <= 2049 ? 12 : 13;
-    if (forced == 8192) l2 = 13;
-    return l2;
-}
 
 // FIRFilter::updateInternals, FIRFilter.cpp:327-354 (host mirror; tables uploaded lazily)
 static void fir_update_internals(pcx_fir *h)
@@ -137,7 +89,55 @@ static int fir_upload_rows(pcx_fir *h, bool integer)
     return PCX_OK;
 }
 
-static bool fir_fast_applicable(const pcx_fir *h) { return h->scalar == PCX_F32 && h->cplx && h->M == 1 && h->L == 1; }
+// Tap i as the frequency-domain pipeline of the element type sees it (floatToQ<QTapsType>, FIRFilter.cpp:348): float64 as it is, float32
+// narrowed to float first, int16 / int8 the Q-format taps exactly as the time-domain kernels use them (int32 / int16).  As a double.
+static std::complex<double> fir_tap(const pcx_fir *h, size_t i)
+{
+    auto q = [&](double t) -> double {
+        switch (h->scalar) {
+        case PCX_F64: return t;
+        case PCX_F32: return (double)(float)t;
+        case PCX_I16: return (double)(int32_t)float_to_q(t, h->scalar, h->qf);
+        default: return (double)(int16_t)float_to_q(t, h->scalar, h->qf);
+        }
+    };
+    return h->ctaps ? std::complex<double>(q(h->taps[2 * i]), q(h->taps[2 * i + 1])) : std::complex<double>(q(h->taps[i]), 0.0);
+}
+
+// Row j of L polyphase rows, h_j[k] = taps[j + k L] (FIRFilter.cpp:341-350); L = 1: the whole tap vector.  A row the tap vector
+// leaves short is simply shorter, and empty where L > ntaps: every table builder sums the taps it is given into zeros, so trailing
+// zero taps (or a single zero for an empty row) change no byte of a table.
+static std::vector<std::complex<double>> fir_row(const pcx_fir *h, size_t j, size_t L)
+{
+    std::vector<std::complex<double>> row;
+    for (size_t i = j; i < h->ntaps; i += L) row.push_back(fir_tap(h, i));
+    return row;
+}
+
+// one table per polyphase row of the handle, `per_row` entries apart
+template <typename T, typename Make>
+static std::vector<T> fir_row_tables(const pcx_fir *h, size_t per_row, Make &&make)
+{
+    std::vector<T> rows(h->L * per_row);
+    for (size_t j = 0; j < h->L; j++) {
+        const std::vector<T> t = make(fir_row(h, j, h->L));
+        std::copy(t.begin(), t.end(), rows.begin() + j * per_row);
+    }
+    return rows;
+}
+
+// int16 / int8: the double transform reproduces the integer convolution bit for bit while ||h_q||_2 < 2^22 (fir_ols_f64.hip), held for
+// every polyphase row (L = 1: the whole tap vector)
+static bool fir_taps_exact(const pcx_fir *h)
+{
+    if (h->scalar != PCX_I16 && h->scalar != PCX_I8) return true;
+    for (size_t j = 0; j < h->L && j < h->ntaps; j++) {
+        double norm2 = 0;
+        for (const std::complex<double> &t : fir_row(h, j, h->L)) norm2 += std::norm(t);
+        if (norm2 >= 17592186044416.0) return false;   // 2^44
+    }
+    return true;
+}
 
 static int fir_sync_tables(pcx_fir *h)
 {
@@ -150,13 +150,10 @@ static int fir_sync_tables(pcx_fir *h)
     case PCX_I16: PCX_TRY(fir_upload_rows<int32_t>(h, true)); break;
     case PCX_I8: PCX_TRY(fir_upload_rows<int16_t>(h, true)); break;
     }
-    h->have_ols = false;
-    h->ols_parts = 0;     // set below by the plans that use them: none may see the value of an earlier configuration
-    h->ols_log2n = 0;
     if (!h->sched.p) {
         PCX_TRY(h->sched.ensure_zeroed(kSchedBytes));
     }
-    if (fir_fast_applicable(h)) {
+    if (h->scalar == PCX_F32 && h->cplx && h->M == 1 && h->L == 1) {
         const size_t K = h->K;
         // reversed, zero-padded complex taps for the LDS-tiled direct kernel
         h->Kp = (K + 7) / 8 * 8;
@@ -167,250 +164,64 @@ static int fir_sync_tables(pcx_fir *h)
             rev[2 * m + 1] = h->ctaps ? (float)h->taps[2 * k + 1] : 0.f;
         }
         PCX_TRY(upload(h->tapsRev, rev));
-        if (K <= kOlsMaxTaps) {
-            std::vector<std::complex<double>> hq(K);
-            for (size_t k = 0; k < K; k++)   // floatToQ<QTapsType>: narrowed to float first (FIRFilter.cpp:348)
-                hq[k] = std::complex<double>((double)(float)(h->ctaps ? h->taps[2 * k] : h->taps[k]),
-                                             h->ctaps ? (double)(float)h->taps[2 * k + 1] : 0.0);
-            h->ols_parts = fir_ols_partitions(K);
-            if (h->ols_parts == 0) {   // the dedicated 4096-sample kernel (fir_ols.hip)
-                PCX_TRY(upload(h->Hspec, make_hspec4096(hq)));
-            } else {                   // the same blocks, the taps in partitions (fir_ols_part.hip)
-                PCX_TRY(upload(h->Hspec, make_hparts(hq, h->ols_parts)));
-            }
-            PCX_TRY(upload(h->tw4096, make_tw4096()));
-            h->have_ols = true;
-        }
     }
-    h->have_ols64 = false;
-    if (h->scalar == PCX_F64 && h->cplx && h->M <= 65535 && h->L == 1 && h->K >= 2 && h->K <= kOls64MaxTaps) {   // M > 1: decimate on store
-        // complex_float64: the same frequency-domain evaluation in double (fir_ols_f64.hip)
-        std::vector<std::complex<double>> hq(h->K);
-        for (size_t k = 0; k < h->K; k++) hq[k] = std::complex<double>(h->ctaps ? h->taps[2 * k] : h->taps[k], h->ctaps ? h->taps[2 * k + 1] : 0.0);
-        h->ols_log2n = fir_ols64_block_log2(h->K);
-        PCX_TRY(upload(h->Hspec, make_hspec<double>(hq, (size_t)1 << h->ols_log2n)));
-        PCX_TRY(upload(h->tw4096, make_tw_ols64(h->ols_log2n)));
-        h->have_ols64 = true;
-    }
-    h->have_ols_int = false;
-    if ((h->scalar == PCX_I16 || h->scalar == PCX_I8) && h->cplx && h->M <= 65535 && h->L == 1 && h->K >= 2 && h->K <= kOls64MaxTaps) {
-        // the Q-format taps exactly as the time-domain kernels use them (floatToQ<QTapsType>, FIRFilter.cpp:348), as doubles;
-        // the double transform reproduces the integer convolution bit for bit while ||h_q||_2 < 2^22 (fir_ols_f64.hip)
-            auto tq = [&](double t) { return h->scalar == PCX_I16 ? (double)(int32_t)float_to_q(t, h->scalar, h->qf) : (double)(int16_t)float_to_q(t, h->scalar, h->qf); };
-        std::vector<std::complex<double>> hq(h->K);
-        double norm2 = 0;
-        for (size_t k = 0; k < h->K; k++) {
-            hq[k] = std::complex<double>(tq(h->ctaps ? h->taps[2 * k] : h->taps[k]), h->ctaps ? tq(h->taps[2 * k + 1]) : 0.0);
-            norm2 += std::norm(hq[k]);
-        }
-        if (norm2 < 17592186044416.0) {   // 2^44
-            h->ols_log2n = fir_ols64_block_log2(h->K);
-            PCX_TRY(upload(h->Hspec, make_hspec<double>(hq, (size_t)1 << h->ols_log2n)));
-            PCX_TRY(upload(h->tw4096, make_tw_ols64(h->ols_log2n)));
-            h->have_ols_int = true;
-        }
-    }
-    h->have_interp64 = false;
-    if ((h->scalar == PCX_F64 || h->scalar == PCX_I16 || h->scalar == PCX_I8) && h->cplx && h->M <= 65535 && h->L > 1 && h->L <= 64 && h->K >= 2 &&
-        h->K <= 2049) {   // M > 1: rational resampling, the interleaving pass keeps one position in M
-        // interpolating filters of these types: every polyphase row h_j[k] = taps[j + k L] (FIRFilter.cpp:341-350) through the
-        // double-precision pipeline into a contiguous workspace row, then one interleaving pass; integers stay exact row by row
-            auto tq = [&](double t) {
-            return h->scalar == PCX_F64 ? t : h->scalar == PCX_I16 ? (double)(int32_t)float_to_q(t, h->scalar, h->qf) : (double)(int16_t)float_to_q(t, h->scalar, h->qf);
-        };
-        std::vector<double> rows(h->L * 2 * 4096);
-        bool ok = true;
-        for (size_t jr = 0; jr < h->L && ok; jr++) {
-            std::vector<std::complex<double>> hq;
-            double norm2 = 0;
-            for (size_t k = 0; k < h->K; k++) {
-                const size_t i = jr + k * h->L;
-                if (i >= h->ntaps) continue;
-                hq.push_back(std::complex<double>(tq(h->ctaps ? h->taps[2 * i] : h->taps[i]), h->ctaps ? tq(h->taps[2 * i + 1]) : 0.0));
-                norm2 += std::norm(hq.back());
-            }
-            if (h->scalar != PCX_F64 && norm2 >= 17592186044416.0) ok = false;
-            if (hq.empty()) hq.push_back(0.0);
-            const std::vector<double> H = make_hspec<double>(hq, 4096);
-            std::copy(H.begin(), H.end(), rows.begin() + jr * 2 * 4096);
-        }
-        if (ok) {
-            PCX_TRY(upload(h->HrowsD, rows));
-            PCX_TRY(upload(h->tw4096, make_tw_ols64(12)));
-            h->ols_log2n = 12;
-            h->have_interp64 = true;
-        }
-    }
-    h->have_interp_real = false;
-    // (real float32 has the float kernel for its rows: have_interp_f32 below)
-    if ((h->scalar == PCX_F64 || h->scalar == PCX_I16 || h->scalar == PCX_I8) && !h->cplx && h->M <= 65535 && h->L > 1 &&
-        h->L <= 64 && h->K >= 2 && h->K <= 2049) {
-            auto tq = [&](double t) {
-            return h->scalar == PCX_F64 ? t : h->scalar == PCX_F32 ? (double)(float)t
-                 : h->scalar == PCX_I16 ? (double)(int32_t)float_to_q(t, h->scalar, h->qf) : (double)(int16_t)float_to_q(t, h->scalar, h->qf);
-        };
-        const bool integer = h->scalar == PCX_I16 || h->scalar == PCX_I8;
-        std::vector<double> rows(h->L * 2 * 4096);
-        bool ok = true;
-        for (size_t jr = 0; jr < h->L && ok; jr++) {
-            std::vector<std::complex<double>> hq;
-            double norm2 = 0;
-            for (size_t k = 0; k < h->K; k++) {
-                const size_t i = jr + k * h->L;
-                if (i >= h->ntaps) continue;
-                hq.push_back(std::complex<double>(tq(h->taps[i]), 0.0));
-                norm2 += std::norm(hq.back());
-            }
-            if (integer && norm2 >= 17592186044416.0) ok = false;
-            if (hq.empty()) hq.push_back(0.0);
-            const std::vector<double> H = make_hspec<double>(hq, 4096);
-            std::copy(H.begin(), H.end(), rows.begin() + jr * 2 * 4096);
-        }
-        if (ok) {
-            PCX_TRY(upload(h->HrowsD, rows));
-            PCX_TRY(upload(h->tw4096, make_tw_ols64(12)));
-            h->ols_log2n = 12;
-            h->have_interp_real = true;
-        }
-    }
-    h->have_interp_f32 = false;
-    if (h->scalar == PCX_F32 && !h->cplx && h->M <= 65535 && h->L > 1 && h->L <= 64 && h->K >= 2 && h->K <= 2049) {
-        // interpolating REAL float32 filters: every polyphase row through the real float kernel (two real blocks per complex transform,
-        // fir_ols.hip) into a workspace row, then the interleaving pass -- instead of the double-precision rows they had shared with
-        // the integer types
-        std::vector<float> rows(h->L * 2 * 4096);
-        for (size_t jr = 0; jr < h->L; jr++) {
-            std::vector<std::complex<double>> hq;
-            for (size_t k = 0; k < h->K; k++) {
-                const size_t i = jr + k * h->L;
-                if (i >= h->ntaps) continue;
-                hq.push_back(std::complex<double>((double)(float)h->taps[i], 0.0));
-            }
-            if (hq.empty()) hq.push_back(0.0);
-            const std::vector<float> H = make_hspec4096(hq);
-            std::copy(H.begin(), H.end(), rows.begin() + jr * 2 * 4096);
-        }
-        PCX_TRY(upload(h->HspecRows, rows));
+
+    FirPlanIn in;
+    in.scalar = h->scalar; in.cplx = h->cplx; in.ctaps = h->ctaps;
+    in.ntaps = h->ntaps; in.L = h->L; in.M = h->M;
+    in.taps16 = h->taps16;
+    in.exact = fir_taps_exact(h);
+    in.ols_int_min = (size_t)PCX_ENV_INT("PCX_OLS_INT_MIN", 0);
+    in.ols_real_min = (size_t)PCX_ENV_INT("PCX_OLS_REAL_MIN", 0);
+    in.ols64_n = (int)PCX_ENV_INT("PCX_OLS64_N", 0);
+    in.decim_fullrate = PCX_ENV_SET("PCX_FIR_DECIM_FULLRATE");
+    in.poly_strided = PCX_ENV_SET("PCX_FIR_POLY_STRIDED");
+    in.slide = PCX_ENV_INT("PCX_FIR_SLIDE", 1) != 0;
+    in.dot2 = PCX_ENV_INT("PCX_FIR_DOT2", 1) != 0;
+    const FirPlan p = h->plan = fir_plan(in);
+
+    // the tables of that plan and of no other
+    const auto whole = [&] { return fir_row(h, 0, 1); };
+    switch (p.ols_plan) {
+    case PCX_FIR_PLAN_CF32_OLS4096: case PCX_FIR_PLAN_F32_OLS4096:
+        PCX_TRY(upload(h->Hspec, make_hspec4096(whole())));
         PCX_TRY(upload(h->tw4096, make_tw4096()));
-        h->have_interp_f32 = true;
-    }
-    h->have_ols_real64 = false;
-    // (real float32 streams have the float kernels: undecimated fir_ols.hip, decimating the partitioned kernel, have_upols_decim below)
-    if ((h->scalar == PCX_F64 || h->scalar == PCX_I16 || h->scalar == PCX_I8) && !h->cplx && h->M <= 65535 &&
-        h->L == 1 && h->K >= 2 && h->K <= kOls64MaxTaps) {
-            std::vector<std::complex<double>> hq(h->K);
-        double norm2 = 0;
-        for (size_t k = 0; k < h->K; k++) {
-            const double t = h->taps[k];
-            hq[k] = h->scalar == PCX_F64 ? t : h->scalar == PCX_F32 ? (double)(float)t
-                    : h->scalar == PCX_I16 ? (double)(int32_t)float_to_q(t, h->scalar, h->qf) : (double)(int16_t)float_to_q(t, h->scalar, h->qf);
-            norm2 += std::norm(hq[k]);
-        }
-        if (h->scalar == PCX_F64 || h->scalar == PCX_F32 || norm2 < 17592186044416.0) {   // integers: ||h_q||_2 < 2^22 keeps the rounded sums exact
-            h->ols_log2n = h->K <= 2049 ? 12 : 13;
-            PCX_TRY(upload(h->Hspec, make_hspec<double>(hq, (size_t)1 << h->ols_log2n)));
-            PCX_TRY(upload(h->tw4096, make_tw_ols64(h->ols_log2n)));
-            h->have_ols_real64 = true;
-        }
-    }
-    h->have_real_ols = false;
-    if (h->scalar == PCX_F32 && !h->cplx && h->M == 1 && h->L == 1 && h->K <= kOlsMaxTaps) {
-        // two real blocks per complex transform (fir_ols.hip); beyond 2049 taps the two halves of the call side by side through the
-        // partitioned kernel (fir_ols_part.hip)
-        std::vector<std::complex<double>> hq(h->K);
-        for (size_t k = 0; k < h->K; k++) hq[k] = std::complex<double>((double)(float)h->taps[k], 0.0);
-        h->ols_parts = fir_ols_partitions(h->K);
-        if (h->ols_parts == 0) PCX_TRY(upload(h->Hspec, make_hspec4096(hq)));
-        else PCX_TRY(upload(h->Hspec, make_hparts(hq, h->ols_parts)));
+        break;
+    case PCX_FIR_PLAN_CF32_UPOLS: case PCX_FIR_PLAN_F32_UPOLS: case PCX_FIR_PLAN_UPOLS_DECIM:
+        PCX_TRY(upload(h->Hspec, make_hparts(whole(), p.parts)));
         PCX_TRY(upload(h->tw4096, make_tw4096()));
-        h->have_real_ols = true;
-    }
-    h->have_upols_decim = false;
-    if (h->scalar == PCX_F32 && h->L == 1 && h->M > 1 && h->M <= 65535 && h->K <= kOlsMaxTaps && (h->K > 2049 || (!h->cplx && h->K >= 2))) {
-        // long DECIMATING filters, complex_float32 or float32: the partitioned kernel at the full rate, one output in M stored
-        // (fir_ols_part.hip) -- the time-domain tile they fell to runs at 1-2 Gsamples/s of input at these tap counts.  REAL float32
-        // decimators of any length take it as well (one partition up to 2049 taps): 300 against the 155 Gsamples/s of the
-        // double-precision pipeline they shared with the integer types
-        std::vector<std::complex<double>> hq(h->K);
-        for (size_t k = 0; k < h->K; k++)
-            hq[k] = std::complex<double>((double)(float)(h->ctaps ? h->taps[2 * k] : h->taps[k]), h->ctaps ? (double)(float)h->taps[2 * k + 1] : 0.0);
-        h->ols_parts = std::max(1, fir_ols_partitions(h->K));
-        PCX_TRY(upload(h->Hspec, make_hparts(hq, h->ols_parts)));
+        break;
+    case PCX_FIR_PLAN_UPOLS_ROWS:
+        PCX_TRY(upload(h->HspecRows, fir_row_tables<float>(h, fir_upols_table_bytes(p.parts) / sizeof(float),
+                                                           [&](const std::vector<std::complex<double>> &r) { return make_hparts(r, p.parts); })));
         PCX_TRY(upload(h->tw4096, make_tw4096()));
-        h->have_upols_decim = true;
-    }
-    h->have_upols_rows = false;
-    if (h->scalar == PCX_F32 && h->L > 1 && h->L <= 64 && h->M <= 65535 && h->K > 2049 && h->K <= kOlsMaxTaps) {
-        // INTERPOLATING filters whose polyphase rows h_j[k] = taps[j + k L] (FIRFilter.cpp:341-350) are longer than 2049 taps: every row
-        // through the partitioned kernel at the input rate into a workspace row, then the interleaving pass (which also keeps one
-        // position in M) -- as the shorter rows go through fir_ols.hip.  A row the tap vector leaves short ends in zeros.
-        const int parts = fir_ols_partitions(h->K);
-        const size_t tb = fir_upols_table_bytes(parts) / sizeof(float);
-        std::vector<float> rows(h->L * tb);
-        for (size_t jr = 0; jr < h->L; jr++) {
-            std::vector<std::complex<double>> hq(h->K, 0.0);
-            for (size_t k = 0; k < h->K; k++) {
-                const size_t i = jr + k * h->L;
-                if (i >= h->ntaps) break;
-                hq[k] = std::complex<double>((double)(float)(h->ctaps ? h->taps[2 * i] : h->taps[i]), h->ctaps ? (double)(float)h->taps[2 * i + 1] : 0.0);
-            }
-            const std::vector<float> T = make_hparts(hq, parts);
-            std::copy(T.begin(), T.end(), rows.begin() + jr * tb);
-        }
-        h->ols_parts = parts;
-        PCX_TRY(upload(h->HspecRows, rows));
+        break;
+    case PCX_FIR_PLAN_F32_OLS4096_ROWS: case PCX_FIR_PLAN_CF32_OLS4096_ROWS: case PCX_FIR_PLAN_CF32_POLY:
+        PCX_TRY(upload(h->HspecRows, fir_row_tables<float>(h, 2 * 4096, make_hspec4096)));
         PCX_TRY(upload(h->tw4096, make_tw4096()));
-        h->have_upols_rows = true;
-    }
-    h->have_poly = false;
-    if (h->scalar == PCX_F32 && h->cplx && (h->L > 1 || h->M > 1) && h->K <= 2049 && h->L <= 64 && h->M < (1u << 17)) {
-        // one spectrum per polyphase row: h_j[k] = taps[j + k*L] (FIRFilter.cpp:341-350)
-        std::vector<float> rows(h->L * 2 * 4096);
-        for (size_t j = 0; j < h->L; j++) {
-            std::vector<std::complex<double>> hq;
-            for (size_t k = 0; k < h->K; k++) {
-                const size_t i = j + k * h->L;
-                if (i >= h->ntaps) continue;
-                hq.push_back(std::complex<double>((double)(float)(h->ctaps ? h->taps[2 * i] : h->taps[i]),
-                                                  h->ctaps ? (double)(float)h->taps[2 * i + 1] : 0.0));
-            }
-            const std::vector<float> H = make_hspec4096(hq);
-            std::copy(H.begin(), H.end(), rows.begin() + j * 2 * 4096);
-        }
-        PCX_TRY(upload(h->HspecRows, rows));
+        break;
+    case PCX_FIR_PLAN_CF32_DECIM:    // the decimator's phase: the output advanced by fold - 1 samples
+        PCX_TRY(upload(h->Hdecim, turn_spectrum_lanes(make_hspec(whole(), 4096, p.fold - 1))));
         PCX_TRY(upload(h->tw4096, make_tw4096()));
-        h->have_poly = true;
-    }
-    h->have_decim = false;
-    // folding pays from 4-fold on (and for M = 2 itself); 2-fold plus a cofactor measured slower than the full-rate kernel
-    // (M = 10: 244 vs 281, M = 50: 251 vs 284 Gsamples/s in; M = 160 = 16 * 10: 373 vs 287)
-    if (h->have_poly && h->L == 1 && (h->M == 2 || fir_decim_fold_factor(h->M) >= 4) && h->M / fir_decim_fold_factor(h->M) <= 65535 &&
-        !PCX_ENV_SET("PCX_FIR_DECIM_FULLRATE")) {
-        // decimating filter: one forward transform, the spectrum folded M-fold, a 4096/M-point inverse (fir_ols_decim.hip).
-        // PCX_FIR_DECIM_FULLRATE (A/B) keeps the full-rate evaluation of the polyphase kernel.
-        std::vector<std::complex<double>> hq(h->K);
-        for (size_t k = 0; k < h->K; k++)
-            hq[k] = std::complex<double>((double)(float)(h->ctaps ? h->taps[2 * k] : h->taps[k]), h->ctaps ? (double)(float)h->taps[2 * k + 1] : 0.0);
-        // even M = M1 * M2: M1 = 16 / 8 / 4 / 2 folded into the spectrum, the cofactor kept one in M2 on the store
-        PCX_TRY(upload(h->Hdecim, turn_spectrum_lanes(make_hspec(hq, 4096, fir_decim_fold_factor(h->M) - 1))));
-        h->have_decim = true;
-    }
-    h->have_interp = false;
-    if (h->have_poly && h->M == 1 && (h->L == 2 || h->L == 4 || h->L == 8 || h->L == 16) && !PCX_ENV_SET("PCX_FIR_DECIM_FULLRATE")) {
-        // interpolating filter: a 4096/L-point forward transform, its spectrum replicated against H of the WHOLE tap vector,
-        // the ordinary 4096-point inverse writing the interleaved output stream (fir_ols_decim.hip)
-        const size_t A = 16 / h->L, kov_in = (h->K - 1 + A - 1) / A * A;
-        if (kov_in <= 4096 / h->L / 2 && h->ntaps <= 2049) {
-            std::vector<std::complex<double>> hq(h->ntaps);
-            for (size_t k = 0; k < h->ntaps; k++)
-                hq[k] = std::complex<double>((double)(float)(h->ctaps ? h->taps[2 * k] : h->taps[k]), h->ctaps ? (double)(float)h->taps[2 * k + 1] : 0.0);
-            PCX_TRY(upload(h->Hdecim, turn_spectrum_lanes(make_hspec(hq, 4096))));
-            h->have_interp = true;
-        }
+        break;
+    case PCX_FIR_PLAN_CF32_INTERP:   // H of the WHOLE tap vector, not of its rows
+        PCX_TRY(upload(h->Hdecim, turn_spectrum_lanes(make_hspec(whole(), 4096))));
+        PCX_TRY(upload(h->tw4096, make_tw4096()));
+        break;
+    case PCX_FIR_PLAN_CF64_OLS: case PCX_FIR_PLAN_REAL64_OLS:
+        PCX_TRY(upload(h->Hspec, make_hspec<double>(whole(), (size_t)1 << p.log2n)));
+        PCX_TRY(upload(h->tw4096, make_tw_ols64(p.log2n)));
+        break;
+    case PCX_FIR_PLAN_CF64_OLS_ROWS: case PCX_FIR_PLAN_REAL64_OLS_ROWS:
+        PCX_TRY(upload(h->HrowsD, fir_row_tables<double>(h, 2 * 4096,
+                                                         [](const std::vector<std::complex<double>> &r) { return make_hspec<double>(r, 4096); })));
+        PCX_TRY(upload(h->tw4096, make_tw_ols64(p.log2n)));
+        break;
     }
     h->dirty = false;
     return PCX_OK;
 }
+
 
 // (internal, pcx_shard.hip) upload the handle's tables now -- every allocation and transfer of the control plane -- instead of at its next call
 namespace pcx {
@@ -527,8 +338,7 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
 // tap: equal in exact arithmetic, not in the transform's rounding.)
 static size_t fir_chunk_quantum(const pcx_fir *h)
 {
-    const bool plain = h->scalar == PCX_F32 && h->cplx && h->M == 1 && h->L == 1 && h->have_ols && h->ols_parts == 0 && h->K > 1;
-    if (plain) return 4096 - (h->K - 1 + 15) / 16 * 16;
+    if (h->plan.ols_plan == PCX_FIR_PLAN_CF32_OLS4096) return 4096 - (h->K - 1 + 15) / 16 * 16;
     return h->M * 4096;
 }
 
@@ -572,33 +382,13 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
     const size_t n_out = (N / h->M) * h->L;
     hipStream_t st = as_stream(stream);
     PCX_TRY(ctx_enter(h->cx, st));
-    int algo = h->algo;
-    const bool fast = fir_fast_applicable(h);
-    if (algo == PCX_FIR_AUTO) {
-        // measured sweep (tools/sweep_fir.py, 16 Mi samples): the frequency-domain kernel runs at
-        // 285-325 Gsamples/s for every K <= 1023 (197 at K = 2049) while the time-domain tile
-        // peaks at 240-256 and falls as 1/K beyond K ~ 48 -- so it is the choice whenever it applies
-        // K == 1 (the block's default unit tap) stays on the time-domain tile: a pass-through
-        // filter must return its input bit for bit, as the reference does
-        if (fast && h->K == 1) algo = PCX_FIR_DIRECT;
-        // decimating complex_float64 / complex_int16 / complex_int8 filters: the full-rate double pipeline with one output in M
-        // stored runs at 130-170 Gsamples/s of input whatever K; the one-output-per-lane kernel it replaces measured 45-129
-        // (int16) / 27-31 (float64) at 63 taps and 12-33 / 6-8 at 255 (tools/decim_int_probe.py)
-        else if ((fast && h->have_ols) || h->have_poly || (h->have_real_ols && h->K > 1) || (h->have_upols_decim && h->K >= 16) || h->have_upols_rows ||
-                 (h->have_ols64 && h->K >= (h->M > 1 ? 16 : kOls64MinTaps)) ||
-                 (h->have_ols_int && h->K >= (h->M > 1 ? 32 : ols_int_min_taps(h->scalar))) ||
-                 (h->have_ols_real64 && h->K >= (h->M > 1 ? 16 : ols_real64_min_taps(h->scalar))) ||
-                 ((h->have_interp64 || h->have_interp_real || h->have_interp_f32) && h->K >= 16)) algo = PCX_FIR_OLS_FFT;
-        // longer than every frequency-domain plan (K > 8193): the sliding-window kernel in the reference's own
-        // operation order -- 8k-term float sums accumulate enough rounding that a reordered sum would sit on the 1e-5 bar
-        else if (fast) algo = h->K > kOlsMaxTaps ? PCX_FIR_EXACT : PCX_FIR_DIRECT;
-        else algo = is_float_scalar(h->scalar) ? PCX_FIR_DIRECT : PCX_FIR_EXACT;
-    }
-    if (algo == PCX_FIR_OLS_FFT && !((fast && h->have_ols) || h->have_poly || h->have_real_ols || h->have_upols_decim || h->have_upols_rows || h->have_ols64 || h->have_ols_int || h->have_ols_real64 ||
-                                     h->have_interp64 || h->have_interp_real || h->have_interp_f32)) {
+    const FirPlan &p = h->plan;
+    const FirChoice ch = fir_resolve(p, h->algo);
+    if (ch.refused) {
         set_error("fir: OLS_FFT needs complex_float32 or float32 and K<=8193 (interpolating: L<=64 rows) or complex_float64 / complex_int16 / complex_int8 with M=L=1, 2<=K<=4097");
         return PCX_ERR_UNSUPPORTED;
     }
+    const int algo = ch.algo;
     int rc;
     // only the samples the N iterations touch: N + K-1
     const size_t used_in = N + h->K - 1;
@@ -607,8 +397,7 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
         // a gated call: only the plain complex_float32 M = L = 1 plan on 4096-sample blocks has the gate (and only its dealt launch,
         // launch_fir_cf32_ols4096 decides).  Anything else: *gated stays 0, nothing has been queued, the caller orders the halo itself.
         // (The one plan that is accepted is named, rather than the others excluded: a plan added later has no gate until it says so.)
-        const bool plain = algo == PCX_FIR_OLS_FFT && fir_fast_applicable(h) && h->have_ols && h->ols_parts == 0;
-        if (!plain) return PCX_OK;
+        if (ch.plan != PCX_FIR_PLAN_CF32_OLS4096) return PCX_OK;
         rc = launch_fir_cf32_ols4096(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->tw4096.p, h->sched.p, st, gate_word, gate_value, gated, h->slots);
         if (rc != PCX_OK || !*gated) return rc;
         h->last_algo = algo;
@@ -617,7 +406,6 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
         *produced = n_out;
         return PCX_OK;
     }
-    int plan;     // PCX_FIR_PLAN_* of the branch taken below (pcx_fir_get_last_plan)
     // interpolation through polyphase ROWS: every row filtered at the input rate into a contiguous workspace row, then one
     // interleaving pass.  Long calls go in batches of iterations so that the workspace stays at kRowsWorkspaceCap bytes
     // whatever the call (it would be a second copy of the output otherwise).
@@ -633,92 +421,82 @@ static int fir_process_dev_impl(pcx_fir *h, const void *in_dev, size_t in_elems,
         }
         return PCX_OK;
     };
-    if (algo == PCX_FIR_OLS_FFT && h->have_interp_f32) {
-        plan = PCX_FIR_PLAN_F32_OLS4096_ROWS;
+    const auto row_of = [](const DevBuf &b, size_t jr, size_t bytes) { return static_cast<const char *>(b.p) + jr * bytes; };
+    const int io64 = h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : 2;     // element type of the double pipeline's loads and stores
+    const FirGeom g{h->L, h->M, h->K, static_cast<const uint32_t *>(h->rowLen.p), h->rowTaps.p};
+    switch (ch.plan) {
+    case PCX_FIR_PLAN_F32_OLS4096_ROWS:
         rc = rows_path(4, h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
-            return launch_fir_f32_ols4096(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HspecRows.p) + jr * 2 * 4096 * sizeof(float), h->K,
-                                          h->tw4096.p, h->sched.p, st);
+            return launch_fir_f32_ols4096(in_b, nb + h->K - 1, dst, nb, row_of(h->HspecRows, jr, 2 * 4096 * sizeof(float)), h->K, h->tw4096.p, h->sched.p, st);
         });
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_interp_real) {
-        plan = PCX_FIR_PLAN_REAL64_OLS_ROWS;
+        break;
+    case PCX_FIR_PLAN_REAL64_OLS_ROWS:
         rc = rows_path(fir_elem_bytes(h), h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
-            return launch_fir_real_ols(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HrowsD.p) + jr * 2 * 4096 * sizeof(double), h->K, 12,
-                                       h->tw4096.p, h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : h->scalar == PCX_I8 ? 2 : 3, 1, qs, st);
+            return launch_fir_real_ols(in_b, nb + h->K - 1, dst, nb, row_of(h->HrowsD, jr, 2 * 4096 * sizeof(double)), h->K, p.log2n, h->tw4096.p, io64, 1, qs, st);
         });
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_interp64) {
-        plan = PCX_FIR_PLAN_CF64_OLS_ROWS;
+        break;
+    case PCX_FIR_PLAN_CF64_OLS_ROWS:
         rc = rows_path(fir_elem_bytes(h), h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
-            return launch_fir_cf64_ols(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HrowsD.p) + jr * 2 * 4096 * sizeof(double), h->K, 12,
-                                       h->tw4096.p, h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : 2, 1, qs, st);
+            return launch_fir_cf64_ols(in_b, nb + h->K - 1, dst, nb, row_of(h->HrowsD, jr, 2 * 4096 * sizeof(double)), h->K, p.log2n, h->tw4096.p, io64, 1, qs, st);
         });
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_ols_real64) {
-        plan = PCX_FIR_PLAN_REAL64_OLS;
-        rc = launch_fir_real_ols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, h->ols_log2n, h->tw4096.p,
-                                 h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : h->scalar == PCX_I8 ? 2 : 3, h->M, qs, st, h->sched.p);
-    } else if (algo == PCX_FIR_OLS_FFT && (h->have_ols64 || h->have_ols_int)) {
-        plan = PCX_FIR_PLAN_CF64_OLS;
-        rc = launch_fir_cf64_ols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, h->ols_log2n, h->tw4096.p,
-                                 h->scalar == PCX_F64 ? 0 : h->scalar == PCX_I16 ? 1 : 2, h->M, qs, st, h->sched.p);
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_upols_rows) {
-        plan = PCX_FIR_PLAN_UPOLS_ROWS;
-        const size_t tb = fir_upols_table_bytes(h->ols_parts);
+        break;
+    case PCX_FIR_PLAN_REAL64_OLS:
+        rc = launch_fir_real_ols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, p.log2n, h->tw4096.p, io64, h->M, qs, st, h->sched.p);
+        break;
+    case PCX_FIR_PLAN_CF64_OLS:
+        rc = launch_fir_cf64_ols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, p.log2n, h->tw4096.p, io64, h->M, qs, st, h->sched.p);
+        break;
+    case PCX_FIR_PLAN_UPOLS_ROWS:
         rc = rows_path(fir_elem_bytes(h), h->M, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
-            return launch_fir_cf32_upols(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HspecRows.p) + jr * tb, h->K, h->ols_parts, h->tw4096.p, st,
+            return launch_fir_cf32_upols(in_b, nb + h->K - 1, dst, nb, row_of(h->HspecRows, jr, fir_upols_table_bytes(p.parts)), h->K, p.parts, h->tw4096.p, st,
                                          !h->cplx, 1);
         });
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_upols_decim) {
-        plan = PCX_FIR_PLAN_UPOLS_DECIM;
-        rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, h->ols_parts, h->tw4096.p, st, !h->cplx, h->M);
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_real_ols && h->ols_parts != 0) {
-        plan = PCX_FIR_PLAN_F32_UPOLS;
-        rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->ols_parts, h->tw4096.p, st, true);
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_real_ols) {
-        plan = PCX_FIR_PLAN_F32_OLS4096;
+        break;
+    case PCX_FIR_PLAN_UPOLS_DECIM:
+        rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, N, h->Hspec.p, h->K, p.parts, h->tw4096.p, st, !h->cplx, h->M);
+        break;
+    case PCX_FIR_PLAN_F32_UPOLS:
+        rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, p.parts, h->tw4096.p, st, true);
+        break;
+    case PCX_FIR_PLAN_F32_OLS4096:
         rc = launch_fir_f32_ols4096(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->tw4096.p, h->sched.p, st);
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_interp) {
-        plan = PCX_FIR_PLAN_CF32_INTERP;
+        break;
+    case PCX_FIR_PLAN_CF32_INTERP:
         rc = launch_fir_cf32_ols4096_interp(in_dev, used_in, out_dev, N, h->Hdecim.p, h->K, h->L, h->tw4096.p, h->sched.p, st);
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_decim) {
-        plan = PCX_FIR_PLAN_CF32_DECIM;
+        break;
+    case PCX_FIR_PLAN_CF32_DECIM:
         rc = launch_fir_cf32_ols4096_decim(in_dev, used_in, out_dev, N, h->Hdecim.p, h->K, h->M, h->tw4096.p, h->sched.p, st);
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_poly && h->M == 1 && h->K <= 2049 && !PCX_ENV_SET("PCX_FIR_POLY_STRIDED")) {
-        plan = PCX_FIR_PLAN_CF32_OLS4096_ROWS;
-        // interpolation by other factors: each polyphase row through the undecimated kernel into a contiguous workspace row,
-        // then one interleaving pass (PCX_FIR_POLY_STRIDED (A/B) keeps the polyphase kernel's stride-L stores)
+        break;
+    case PCX_FIR_PLAN_CF32_OLS4096_ROWS:
         rc = rows_path(8, 1, [&](const void *in_b, size_t nb, void *dst, size_t jr) {
-            return launch_fir_cf32_ols4096(in_b, nb + h->K - 1, dst, nb, static_cast<const char *>(h->HspecRows.p) + jr * 2 * 4096 * sizeof(float), h->K,
-                                           h->tw4096.p, h->sched.p, st);
+            return launch_fir_cf32_ols4096(in_b, nb + h->K - 1, dst, nb, row_of(h->HspecRows, jr, 2 * 4096 * sizeof(float)), h->K, h->tw4096.p, h->sched.p, st);
         });
-    } else if (algo == PCX_FIR_OLS_FFT && h->have_poly) {
-        plan = PCX_FIR_PLAN_CF32_POLY;
+        break;
+    case PCX_FIR_PLAN_CF32_POLY:
         rc = launch_fir_cf32_ols4096_poly(in_dev, used_in, out_dev, N, h->HspecRows.p, h->K, h->L, h->M, h->tw4096.p, st);
-    } else if (algo == PCX_FIR_OLS_FFT && h->ols_parts != 0) {
-        plan = PCX_FIR_PLAN_CF32_UPOLS;
-        rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->ols_parts, h->tw4096.p, st);
-    } else if (algo == PCX_FIR_OLS_FFT) {
-        plan = PCX_FIR_PLAN_CF32_OLS4096;
+        break;
+    case PCX_FIR_PLAN_CF32_UPOLS:
+        rc = launch_fir_cf32_upols(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, p.parts, h->tw4096.p, st);
+        break;
+    case PCX_FIR_PLAN_CF32_OLS4096:
         rc = launch_fir_cf32_ols4096(in_dev, used_in, out_dev, n_out, h->Hspec.p, h->K, h->tw4096.p, h->sched.p, st, nullptr, 0, nullptr, h->slots, h->lead_valid);
-    } else if (algo == PCX_FIR_DIRECT && fast && (2048 + h->Kp + 8) * 9 / 8 * 8 + 64 <= 64 * 1024) {
-        plan = PCX_FIR_PLAN_CF32_DIRECT_TILE;
-        // the LDS-tiled time-domain kernel while its tile (2048 outputs + taps) fits; longer filters than every
-        // fast plan (K > 8193) take the sliding-window kernel below
+        break;
+    case PCX_FIR_PLAN_CF32_DIRECT_TILE:
         rc = launch_fir_cf32_direct(in_dev, used_in, out_dev, n_out, h->tapsRev.p, h->K, h->Kp, st);
-    } else {
-        FirGeom g{h->L, h->M, h->K, static_cast<const uint32_t *>(h->rowLen.p), h->rowTaps.p};
-        // PCX_FIR_SLIDE=0 keeps the one-output-per-lane kernel for M = L = 1 too (A/B)
-        const int slide = (int)PCX_ENV_INT("PCX_FIR_SLIDE", 1);
-        // PCX_FIR_DOT2=0 keeps complex_int16 on the 24-bit multiply path (A/B)
-        const int dot2 = (int)PCX_ENV_INT("PCX_FIR_DOT2", 1);
-        if (slide && dot2 && h->taps16 && h->L == 1 && h->M == 1 && h->K <= 12000)
-            plan = PCX_FIR_PLAN_DOT2, rc = launch_fir_ci16_dot2(in_dev, out_dev, n_out, h->K, h->tapsP.p, h->scalar == PCX_I8, qs, st);
-        else if (slide && h->L == 1 && h->M == 1)
-            plan = PCX_FIR_PLAN_SLIDE, rc = launch_fir_slide(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, h->taps24, g, in_dev, out_dev, n_out, qs, st);
-        else
-            plan = PCX_FIR_PLAN_GENERIC, rc = launch_fir_generic(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, g, in_dev, out_dev, n_out, qs, st);
+        break;
+    case PCX_FIR_PLAN_DOT2:
+        rc = launch_fir_ci16_dot2(in_dev, out_dev, n_out, h->K, h->tapsP.p, h->scalar == PCX_I8, qs, st);
+        break;
+    case PCX_FIR_PLAN_SLIDE:
+        rc = launch_fir_slide(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, h->taps24, g, in_dev, out_dev, n_out, qs, st);
+        break;
+    default:   // PCX_FIR_PLAN_GENERIC
+        rc = launch_fir_generic(h->scalar, h->cplx, h->ctaps, algo == PCX_FIR_EXACT, g, in_dev, out_dev, n_out, qs, st);
+        break;
     }
     if (rc != PCX_OK) return rc;
     h->last_algo = algo;
-    h->last_plan = plan;
+    h->last_plan = ch.plan;
     *consumed = N;
     *produced = n_out;
     return PCX_OK;

@@ -1,8 +1,8 @@
 """The table of FIR plans that tests/test_fir_plans_gpu.py, tests/test_fir_truth_cpu.py and tests/test_fir_truth_gpu.py share.
 
-fir_process_dev_impl (pothoscomms_amd/csrc/pcx_fir_api.hip) picks one of about twenty plans from the handle's tables, and the
-AUTO choice above it picks the algorithm.  PLANS holds at least one row for each branch of both, and a row on either side of every
-bound that decides a plan.  Each row names the last_algo and the last_plan its call must report; _taps and _stream give the row's own
+The planner (pothoscomms_amd/csrc/fir_plan.hpp) picks one of about twenty plans from the handle's settings, and the algorithm AUTO
+stands for.  PLANS holds at least one row for each plan and each answer of AUTO, and a row on either side of every bound that
+decides a plan.  Each row names the last_algo and the last_plan its call must report; _taps and _stream give the row's own
 seeded taps and input.  (A plain module: nothing here needs a GPU.)
 """
 import collections
@@ -19,12 +19,12 @@ def R(name, dtype, taps, ntaps, L=1, M=1, algo="AUTO", want="OLS_FFT", bar=None,
     return Row(name, dtype, taps, ntaps, L, M, algo, want, bar, tapgen, plan)
 
 
-# plan: the name (pothoscomms_amd._lib.FIR_PLANS) that FirFilter.last_plan must report after the row's call: the branch of
-# fir_process_dev_impl that ran, where last_algo says only which of three algorithms
+# plan: the name (pothoscomms_amd._lib.FIR_PLANS) that FirFilter.last_plan must report after the row's call: the plan
+# fir_resolve (fir_plan.hpp) gave the call, where last_algo says only which of three algorithms
 # bar: None = the default of the type (integers and EXACT bit for bit, float64 1e-13, float32 TOL); a number = the float32 bar of
 # that plan's own parity test (tests/test_parity_gpu.py, tests/test_fuzz_gpu.py)
 PLANS = [
-    # -- complex_float32, M = L = 1 (fir_fast_applicable) --
+    # -- complex_float32, M = L = 1 --
     R("cf32 direct tile K=1 (AUTO: the unit tap stays exact)", "complex_float32", "COMPLEX", 1, want="DIRECT", plan="CF32_DIRECT_TILE"),
     R("cf32 direct tile K=255 DIRECT", "complex_float32", "COMPLEX", 255, algo="DIRECT", want="DIRECT", plan="CF32_DIRECT_TILE"),
     R("cf32 4096-sample K=1 OLS_FFT", "complex_float32", "COMPLEX", 1, algo="OLS_FFT", plan="CF32_OLS4096"),
@@ -35,7 +35,7 @@ PLANS = [
     R("cf32 partitioned K=4097", "complex_float32", "COMPLEX", 4097, plan="CF32_UPOLS"),
     R("cf32 partitioned K=8193", "complex_float32", "COMPLEX", 8193, plan="CF32_UPOLS"),
     R("cf32 sliding EXACT K=8194 (beyond every frequency-domain plan)", "complex_float32", "COMPLEX", 8194, want="EXACT", plan="SLIDE"),
-    # -- complex_float32 decimating: the folded spectrum (have_decim) for M = 2 and 4 / 8 / 16-fold, the strided polyphase kernel else --
+    # -- complex_float32 decimating: the folded spectrum (CF32_DECIM) for M = 2 and 4 / 8 / 16-fold, the strided polyphase kernel else --
     R("cf32 decim M=2", "complex_float32", "COMPLEX", 63, M=2, plan="CF32_DECIM"),
     R("cf32 decim M=4", "complex_float32", "REAL", 100, M=4, plan="CF32_DECIM"),
     R("cf32 decim M=8", "complex_float32", "COMPLEX", 255, M=8, plan="CF32_DECIM"),
@@ -45,7 +45,7 @@ PLANS = [
     R("cf32 poly strided M=3", "complex_float32", "COMPLEX", 100, M=3, plan="CF32_POLY"),
     R("cf32 poly strided M=6 (2-fold: not folded)", "complex_float32", "REAL", 100, M=6, plan="CF32_POLY"),
     R("cf32 poly strided L=3 M=2", "complex_float32", "COMPLEX", 61, L=3, M=2, plan="CF32_POLY"),
-    # -- complex_float32 interpolating: the replicated spectrum (have_interp, L in 2/4/8/16), polyphase rows otherwise --
+    # -- complex_float32 interpolating: the replicated spectrum (CF32_INTERP, L in 2/4/8/16), polyphase rows otherwise --
     R("cf32 interp L=2", "complex_float32", "COMPLEX", 64, L=2, plan="CF32_INTERP"),
     R("cf32 interp L=4 K=513 (kov_in = 512, at its bound)", "complex_float32", "COMPLEX", 2049, L=4, plan="CF32_INTERP"),
     R("cf32 interp L=8", "complex_float32", "COMPLEX", 200, L=8, plan="CF32_INTERP"),
@@ -62,12 +62,12 @@ PLANS = [
     R("f32 sliding K=1", "float32", "REAL", 1, want="DIRECT", plan="SLIDE"),
     R("f32 real ols K=2049", "float32", "REAL", 2049, plan="F32_OLS4096"),
     R("f32 real ols partitioned K=2050", "float32", "REAL", 2050, bar=3 * TOL, plan="F32_UPOLS"),
-    # -- float32 interpolating rows on the float kernel (have_interp_f32, 16 <= K <= 2049 under AUTO) --
+    # -- float32 interpolating rows on the float kernel (F32_OLS4096_ROWS, 16 <= K <= 2049 under AUTO) --
     R("f32 generic L=3 K=15 (below the interpolating rows)", "float32", "REAL", 45, L=3, want="DIRECT", plan="GENERIC"),
     R("f32 interp rows L=3 K=16", "float32", "REAL", 46, L=3, plan="F32_OLS4096_ROWS"),
     R("f32 interp rows L=5 M=3 K=16", "float32", "REAL", 80, L=5, M=3, plan="F32_OLS4096_ROWS"),
     R("f32 interp rows L=5 M=3 K=2049", "float32", "REAL", 10245, L=5, M=3, plan="F32_OLS4096_ROWS"),
-    # -- complex_float64 (have_ols64 from K = 4, M > 1 from 16; have_interp64 to L = 64) --
+    # -- complex_float64 (CF64_OLS from K = 4, M > 1 from 16; CF64_OLS_ROWS to L = 64) --
     R("cf64 sliding K=3", "complex_float64", "COMPLEX", 3, want="DIRECT", plan="SLIDE"),
     R("cf64 ols K=4", "complex_float64", "COMPLEX", 4, plan="CF64_OLS"),
     R("cf64 ols K=2049 (4096 block)", "complex_float64", "REAL", 2049, plan="CF64_OLS"),
@@ -80,7 +80,7 @@ PLANS = [
     R("cf64 generic M=65536 (past the decimating plans)", "complex_float64", "COMPLEX", 16, M=65536, want="DIRECT", plan="GENERIC"),
     R("cf64 interp64 L=64", "complex_float64", "COMPLEX", 1280, L=64, plan="CF64_OLS_ROWS"),
     R("cf64 generic L=65", "complex_float64", "COMPLEX", 1300, L=65, want="DIRECT", plan="GENERIC"),
-    # -- complex_int16 (have_ols_int from 64 taps while ||h_q||^2 < 2^44; the packed dot-product kernel below) --
+    # -- complex_int16 (CF64_OLS from 64 taps while ||h_q||^2 < 2^44; the packed dot-product kernel below) --
     R("ci16 dot2 K=40", "complex_int16", "COMPLEX", 40, want="EXACT", tapgen="q16", plan="DOT2"),
     R("ci16 sliding K=63 real taps", "complex_int16", "REAL", 63, want="EXACT", plan="SLIDE"),
     R("ci16 ols K=64", "complex_int16", "COMPLEX", 64, plan="CF64_OLS"),
@@ -94,13 +94,13 @@ PLANS = [
     R("ci16 ols decim M=2 K=32", "complex_int16", "COMPLEX", 32, M=2, plan="CF64_OLS"),
     R("ci16 interp64 L=64", "complex_int16", "COMPLEX", 1280, L=64, plan="CF64_OLS_ROWS"),
     R("ci16 interp64 L=3 M=2", "complex_int16", "COMPLEX", 60, L=3, M=2, plan="CF64_OLS_ROWS"),
-    # -- complex_int8 (have_ols_int from 96 taps) --
+    # -- complex_int8 (CF64_OLS from 96 taps) --
     R("ci8 dot2 K=40", "complex_int8", "COMPLEX", 40, want="EXACT", plan="DOT2"),
     R("ci8 dot2 K=95", "complex_int8", "COMPLEX", 95, want="EXACT", plan="DOT2"),
     R("ci8 ols K=96", "complex_int8", "COMPLEX", 96, plan="CF64_OLS"),
     R("ci8 interp64 L=64", "complex_int8", "COMPLEX", 1280, L=64, plan="CF64_OLS_ROWS"),
     R("ci8 generic L=65", "complex_int8", "COMPLEX", 1300, L=65, want="EXACT", plan="GENERIC"),
-    # -- REAL float64 / int16 / int8 on the double pipeline (have_ols_real64 from 24 / 48 taps, M > 1 from 16; have_interp_real) --
+    # -- REAL float64 / int16 / int8 on the double pipeline (REAL64_OLS from 24 / 48 taps, M > 1 from 16; REAL64_OLS_ROWS) --
     R("f64 sliding K=23", "float64", "REAL", 23, want="DIRECT", plan="SLIDE"),
     R("f64 real ols K=24", "float64", "REAL", 24, plan="REAL64_OLS"),
     R("f64 real ols K=4097 (8192 block)", "float64", "REAL", 4097, plan="REAL64_OLS"),

@@ -1,7 +1,7 @@
 """Every plan of pcx_fir_process_dev through one table.
 
-fir_process_dev_impl (pothoscomms_amd/csrc/pcx_fir_api.hip) picks one of about twenty plans from the handle's tables, and the
-AUTO choice above it picks the algorithm.  PLANS (tests/fir_plans.py) holds at least one row for each branch of both, and a row on
+The planner (pothoscomms_amd/csrc/fir_plan.hpp) picks one of about twenty plans from the handle's settings, and the algorithm AUTO
+stands for.  PLANS (tests/fir_plans.py) holds at least one row for each plan and each answer of AUTO, and a row on
 either side of every bound that decides a plan.  Each row names the last_algo and the last_plan the call must report.  Three checks
 run over the table:
 
