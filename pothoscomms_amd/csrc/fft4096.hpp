@@ -200,6 +200,96 @@ __device__ __forceinline__ void fft16_tw_conj(cf (&v)[16], const LaneTw &tw)
 #pragma unroll
     for (int k1 = 0; k1 < 4; k1++) fft4_conj(v[4 * k1], v[4 * k1 + 1], v[4 * k1 + 2], v[4 * k1 + 3]);
 }
+// ---- folded butterflies: the multiply in front of a butterfly rides on the butterfly's own additions ----
+// p = a + w b, q = a - w b  as  p = fma(b.xx, w, fma(b.yy, (-w.y, w.x), a)), q = 2 a - p: three packed instructions where the
+// multiply (2) and the two additions take four.  With both operands multiplied, m = wa a (2), p = m + wb b (2), q = 2 m - p (1): five
+// for six.  Only a pass that multiplies BEFORE its butterflies can take the form -- the decimation-in-time passes of the overlap-save
+// inverse (dit_back) -- and only they do: fft16_tw / fft16_tw_conj / fft16_plain above serve everything else unchanged.
+// One rounding moves: q takes p's rounding error along (p: 0.64 u rms against 0.68 u, q: 0.81 u against 0.68 u on random butterflies).
+// Written as ONE asm block per DFT4, its two chains interleaved: between single-instruction asm statements the compiler puts a
+// wait state (s_nop 0) after every result the next statement reads -- 110 per block, more than the fold saves.
+// The operand modifiers, b times w accumulated on c in two halves:
+//   IM   (c.x - b.y w.y, c.y + b.x w.y)    op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]
+//   RE   (c.x + b.x w.x, c.y + b.y w.x)    op_sel:[0,0,0] op_sel_hi:[1,0,1]
+// and for conj(h b) (the modifiers of cmul2_conj):
+//   IMC  (c.x - b.y h.y, c.y - b.x h.y)    IM with neg_hi:[0,1,0] as well
+//   REC  (c.x + b.x h.x, c.y - b.y h.x)    RE with neg_hi:[1,0,0]
+// 2 a - p takes the inline constant 2.0: for a packed float32 operand it sits in the operand's LOW half, op_sel_hi = 0 reads it
+// for both halves.
+#define PCX_FOLD_IM0 " op_sel:[1,1] op_sel_hi:[0,1] neg_lo:[0,1]"
+#define PCX_FOLD_IM " op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]"
+#define PCX_FOLD_RE " op_sel:[0,0,0] op_sel_hi:[1,0,1]"
+#define PCX_FOLD_IMC0 " op_sel:[1,1] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]"
+#define PCX_FOLD_IMC " op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0] neg_hi:[0,1,0]"
+#define PCX_FOLD_REC " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_hi:[1,0,0]"
+#define PCX_FOLD_2AMP " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]"
+// forward DFT4 of (a0, w1 a1, w2 a2, w3 a3) in place, 12 packed instructions for the 14 of three multiplies and eight additions;
+// CONJ: conjugated outputs, the modifiers of fft4_conj on the last four.  The whole DFT4 is one block: a compiler-made addition
+// behind the block would take a wait state as well.
+//   t0 = a0 + w2 a2 -> a2, t1 = 2 a0 - t0 -> a0, m = w1 a1, t2 = m + w3 a3 -> a3, d = 2 m - t2 -> a1; then the four additions
+template <bool CONJ>
+__device__ __forceinline__ void fft4_fold(cf &a0, cf &a1, cf &a2, cf &a3, cf w1, cf w2, cf w3)
+{
+    cf t, m;
+#define PCX_FOLD_HEAD                                                                                                             \
+    "v_pk_mul_f32 %5, %1, %6" PCX_FOLD_IM0 "\n\t"                                                                                 \
+    "v_pk_fma_f32 %4, %2, %7, %0" PCX_FOLD_IM "\n\t"                                                                              \
+    "v_pk_fma_f32 %5, %1, %6, %5" PCX_FOLD_RE "\n\t"                                                                              \
+    "v_pk_fma_f32 %2, %2, %7, %4" PCX_FOLD_RE "\n\t"                                                                              \
+    "v_pk_fma_f32 %1, %3, %8, %5" PCX_FOLD_IM "\n\t"                                                                              \
+    "v_pk_fma_f32 %0, %0, 2.0, %2" PCX_FOLD_2AMP "\n\t"                                                                           \
+    "v_pk_fma_f32 %3, %3, %8, %1" PCX_FOLD_RE "\n\t"                                                                              \
+    "v_pk_fma_f32 %1, %5, 2.0, %3" PCX_FOLD_2AMP "\n\t"
+    if (CONJ) {
+        asm(PCX_FOLD_HEAD
+            "v_pk_add_f32 %4, %2, %3 neg_hi:[1,1]\n\t"                                        // ( t0.x + t2.x, -t0.y - t2.y)
+            "v_pk_add_f32 %2, %2, %3 neg_lo:[0,1] neg_hi:[1,0]\n\t"                           // ( t0.x - t2.x, -t0.y + t2.y)
+            "v_pk_add_f32 %5, %0, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[1,0]\n\t"           // ( t1.x + d.y,  -t1.y + d.x )
+            "v_pk_add_f32 %3, %0, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[1,1]"  // ( t1.x - d.y,  -t1.y - d.x )
+            : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(t), "=&v"(m)
+            : "v"(w1), "v"(w2), "v"(w3));
+    } else {
+        asm(PCX_FOLD_HEAD
+            "v_pk_add_f32 %4, %2, %3\n\t"                                                     // t0 + t2
+            "v_pk_add_f32 %2, %2, %3 neg_lo:[0,1] neg_hi:[0,1]\n\t"                           // t0 - t2
+            "v_pk_add_f32 %5, %0, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]\n\t"           // t1 + (-i) d
+            "v_pk_add_f32 %3, %0, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]"               // t1 - (-i) d
+            : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(t), "=&v"(m)
+            : "v"(w1), "v"(w2), "v"(w3));
+    }
+#undef PCX_FOLD_HEAD
+    a0 = t;
+    a1 = m;
+}
+// fft16_tw / fft16_tw_conj with both layers of lane factors folded: 96 packed instructions for 112, same factors, same output order
+template <bool CONJ>
+__device__ __forceinline__ void fft16_tw_fold(cf (&v)[16], const LaneTw &tw)
+{
+#pragma unroll
+    for (int n2 = 0; n2 < 4; n2++) fft4_fold<false>(v[n2], v[4 + n2], v[8 + n2], v[12 + n2], tw.a[0], tw.a[1], tw.a[2]);
+#pragma unroll
+    for (int k1 = 0; k1 < 4; k1++) fft4_fold<CONJ>(v[4 * k1], v[4 * k1 + 1], v[4 * k1 + 2], v[4 * k1 + 3], tw.c[k1], tw.c[4 + k1], tw.c[8 + k1]);
+}
+// fft16_plain behind its inner layer (a caller that has folded a multiply of its own into that layer: ols_block.hpp
+// spectrum_times_h_inner): the W16 constants and the outer layer
+__device__ __forceinline__ void fft16_plain_outer(cf (&v)[16])
+{
+    constexpr float C1 = 0.92387953251128673848f;  // cos(pi/8)
+    constexpr float S1 = 0.38268343236508978178f;  // sin(pi/8)
+    constexpr float R2 = 0.70710678118654752440f;  // cos(pi/4)
+    v[4 * 1 + 1] = cmul_cs(v[4 * 1 + 1], C1, S1);    // e = 1
+    v[4 * 1 + 2] = cmul_cs(v[4 * 1 + 2], R2, R2);    // e = 2
+    v[4 * 1 + 3] = cmul_cs(v[4 * 1 + 3], S1, C1);    // e = 3
+    v[4 * 2 + 1] = cmul_cs(v[4 * 2 + 1], R2, R2);    // e = 2
+    v[4 * 2 + 3] = cmul_cs(v[4 * 2 + 3], -R2, R2);   // e = 6
+    v[4 * 3 + 1] = cmul_cs(v[4 * 3 + 1], S1, C1);    // e = 3
+    v[4 * 3 + 2] = cmul_cs(v[4 * 3 + 2], -R2, R2);   // e = 6
+    v[4 * 3 + 3] = cmul_cs(v[4 * 3 + 3], -C1, -S1);  // e = 9
+    fft4(v[0], v[1], v[2], v[3]);
+    fft4(v[4], v[5], v[6], v[7]);
+    fft4_mi2(v[8], v[9], v[10], v[11]);
+    fft4(v[12], v[13], v[14], v[15]);
+}
 // register index q holds output bin k = bin_of(q)
 __device__ __forceinline__ constexpr int bin_of(int q) { return (q >> 2) + 4 * (q & 3); }
 
@@ -545,11 +635,14 @@ __device__ __forceinline__ void dif_rest(cf (&v)[16], cf *lds, int j, HOOK befor
 }
 // inverse on conjugated input: u[r] = conj(Y)[spec_lane(j) + 256 r] on entry, u[q] = IFFT(Y)[j + 256 bin_of(q)] on exit
 // (CONJ = false: conj(IFFT(Y)), for a kernel that wants the conjugate anyway)
-template <bool CONJ = true>
+// FOLD: the folded butterflies in both twiddled passes, and u comes in BEHIND the inner layer of the first sixteen-point transform
+// (spectrum_times_h_inner has run it, H folded in)
+template <bool CONJ = true, bool FOLD = false>
 __device__ __forceinline__ void dit_back(cf (&u)[16], cf *lds, int j, const LaneTw &tw3)
 {
     const int row = 272 * (j >> 4), l = j & 15;
-    fft16_plain(u);
+    if (FOLD) fft16_plain_outer(u);
+    else fft16_plain(u);
     wave_lds_order();
 #pragma unroll
     for (int q = 0; q < 16; q++) lds[row + 17 * l + bin_of(q)] = u[q];
@@ -558,14 +651,16 @@ __device__ __forceinline__ void dit_back(cf (&u)[16], cf *lds, int j, const Lane
     for (int r = 0; r < 16; r++) u[r] = lds[row + l + 17 * r];
     LaneTw tw2;
     load_pass2_twiddles(tw2, lds, j);
-    fft16_tw(u, tw2);
+    if (FOLD) fft16_tw_fold<false>(u, tw2);
+    else fft16_tw(u, tw2);
     wave_lds_order();
 #pragma unroll
     for (int q = 0; q < 16; q++) lds[row + l + 16 * bin_of(q)] = u[q];
     lds_barrier();
 #pragma unroll
     for (int r = 0; r < 16; r++) u[r] = lds[j + 272 * r];
-    if (CONJ) fft16_tw_conj(u, tw3);
+    if (FOLD) fft16_tw_fold<CONJ>(u, tw3);
+    else if (CONJ) fft16_tw_conj(u, tw3);
     else fft16_tw(u, tw3);
 }
 

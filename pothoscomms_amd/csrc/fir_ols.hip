@@ -49,7 +49,10 @@ namespace pcx {
 // -- room for the register prefetch at 4 workgroups per CU.
 // XCH: 1 = the transform pair with its second exchange inside sixteen lanes (fft4096.hpp: three barriers per block), 0 = the
 // Stockham passes both ways (eight)
-template <bool PREFETCH, unsigned LROWS = fft4k::kRowsAll, unsigned SROWS = fft4k::kRowsAll, int SAUX = 2, int CHUNKED = 0, int DIAG = 0, bool HGLOBAL = false, bool GATED = false, int XCH = 0>
+// FOLD (with XCH): the inverse on the folded butterflies -- the H multiply and both layers of lane factors ride on the butterflies' own
+// additions (fft4096.hpp fft4_fold, ols_block.hpp spectrum_times_h_inner): 600 packed instructions per block for 640; the forward
+// half is untouched.  Product A/B, 255 taps: 0.1851-0.1860 ms against 0.1879-0.1886 (profiles/r09/ab_fold.txt)
+template <bool PREFETCH, unsigned LROWS = fft4k::kRowsAll, unsigned SROWS = fft4k::kRowsAll, int SAUX = 2, int CHUNKED = 0, int DIAG = 0, bool HGLOBAL = false, bool GATED = false, int XCH = 0, bool FOLD = false>
 __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_ols4096_kernel(const float2 *__restrict__ in, size_t in_elems,
                                                                   float2 *__restrict__ out, size_t n_out,
                                                                   const float2 *__restrict__ Hspec, int Kov, int pad,
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_
         for (int k = 0; k < 16; k++) H[k] = reinterpret_cast<const cf *>(Hspec)[j + 256 * k];
     }
     static_assert(!XCH || (DIAG == 0 && !HGLOBAL), "the sixteen-lane exchange is built for the product configuration only");
+    static_assert(!FOLD || XCH, "the folded butterflies are built into dit_back only");
     cf nx[16];
     if (PREFETCH) fetch(nx, b);
     for (; b < bend; b += bstep) {
@@ -178,13 +182,14 @@ __global__ __launch_bounds__(256, (PREFETCH && !HGLOBAL) ? 3 : 4) void fir_cf32_
 #pragma unroll
             for (int k = 0; k < 16; k++) H[k] = Hp[j + 256 * k];
         }
-        spectrum_times_h(u, v, H);
+        if (FOLD) spectrum_times_h_inner(u, v, H);      // with the inner layer of the inverse's first transform (ols_block.hpp)
+        else spectrum_times_h(u, v, H);
         if (CHUNKED == 3) deal.publish(j);  // the inverse passes' barriers stand between this and deal.advance()
         // second half of a block ahead of other workgroups' first halves (priority, then age, decides VALU issue between the four
         // waves of a SIMD): blocks already half done retire -- and free their loads' successors -- sooner.  Measured +1.7 %
         // (tools/ols_lab.hip "prio 1 on inverse + stores": 0.2060 -> 0.2023 ms); graded or higher levels measured the same.
         __builtin_amdgcn_s_setprio(1);
-        if (XCH) dit_back(u, lds, j, tw3);
+        if (XCH) dit_back<true, FOLD>(u, lds, j, tw3);
         else if (DIAG != 2) {
         pass1<PART>(u, lds, j);
         pass2<PART>(u, lds, j);
@@ -243,6 +248,7 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
     const int align = (int)PCX_ENV_INT("PCX_OLS_ALIGN", 1);
 #ifdef PCX_DIAG
     const long near_rows = PCX_ENV_INT("PCX_OLS_NEAR_ROWS", 0);     // 1 / 2: ONE / TWO normally cached rows at either end of the window in place of the default mix (below)
+    const bool fold = PCX_ENV_INT("PCX_OLS_FOLD", 1) != 0;          // 0: the inverse on the multiply-then-add pair of the rounds before (below)
 #else
     constexpr long near_rows = 0;
 #endif
@@ -329,12 +335,19 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
     // MIX keeps ONE row at either end: it serves Kov <= 256, the larger overlaps keep the kernels they had.
     // PCX_OLS_NEAR_ROWS=1 / 2 (diag) bring the one-row / two-row policies of the rounds before back, for A/B
     // One policy = three instantiations: the gated dealt, the dealt and the grid-stride kernel.
-#define PCX_OLS_POLICY(LROWS)                                                                                                       \
+    // FOLD: the inverse transform on the folded butterflies (fft4096.hpp), every product instantiation.  PCX_OLS_FOLD=0 (diag) brings
+    // the multiply-then-add pair of the rounds before back, for A/B
+#define PCX_OLS_POLICY_F(LROWS, FOLD)                                                                                               \
     do {                                                                                                                            \
-        if (dealt && gate.word) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 3, 0, false, true, 1>), gd);         \
-        else if (dealt) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 3, 0, false, false, 1>), gd);                \
-        else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 0, 0, false, false, 1>), g4);                           \
+        if (dealt && gate.word) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 3, 0, false, true, 1, FOLD>), gd);   \
+        else if (dealt) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 3, 0, false, false, 1, FOLD>), gd);          \
+        else PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, LROWS, NONE, 2, 0, 0, false, false, 1, FOLD>), g4);                     \
     } while (0)
+#ifdef PCX_DIAG
+#define PCX_OLS_POLICY(LROWS) do { if (fold) PCX_OLS_POLICY_F(LROWS, true); else PCX_OLS_POLICY_F(LROWS, false); } while (0)
+#else
+#define PCX_OLS_POLICY(LROWS) PCX_OLS_POLICY_F(LROWS, true)
+#endif
 #ifdef PCX_DIAG
     if (dealt && !gate.word && PCX_ENV_INT("PCX_OLS_XCH", 1) == 0) {       // the eight-barrier Stockham pair, for A/B
         if (Kov <= 256) PCX_OLS_LAUNCH((fir_cf32_ols4096_kernel<false, E1, NONE, 2, 3>), gd);
@@ -347,6 +360,7 @@ int launch_fir_cf32_ols4096(const void *in, size_t in_elems, void *out, size_t n
     else if (Kov <= 1024) PCX_OLS_POLICY(E4);
     else PCX_OLS_POLICY(ALL);
 #undef PCX_OLS_POLICY
+#undef PCX_OLS_POLICY_F
 #ifdef PCX_DIAG
 launched:
 #endif
@@ -608,7 +622,7 @@ int launch_interleave_rows_cf32(const void *rows, void *out, size_t n, size_t L,
 // sample (8 in, 4 out).  The overlap is rounded up to a multiple of 32 samples (aligned 1 KiB
 // output rows); 128 VGPRs, 4 workgroups per CU.
 // --------------------------------------------------------------------------------- //
-template <int OCC, int NOV, unsigned LROWS, unsigned SROWS, int SAUX, bool DYN = false, bool GATED = false>
+template <int OCC, int NOV, unsigned LROWS, unsigned SROWS, int SAUX, bool DYN = false, bool GATED = false, bool FOLD = false>
 __global__ __launch_bounds__(256, OCC) void fmchain_cf32_ols4096_kernel(const float2 *__restrict__ in, size_t in_elems,
                                                                         float *__restrict__ out, size_t n_out,
                                                                         const float2 *__restrict__ Hspec, int K, int pad,
@@ -666,10 +680,11 @@ __global__ __launch_bounds__(256, OCC) void fmchain_cf32_ols4096_kernel(const fl
         if (DYN) deal.draw(j);              // behind the first butterflies (pcx_sched.hpp)
         dif_rest(v, lds, j);
         cf u[16];
-        spectrum_times_h(u, v, H);
+        if (FOLD) spectrum_times_h_inner(u, v, H);      // with the inner layer of the inverse's first transform (ols_block.hpp)
+        else spectrum_times_h(u, v, H);
         if (DYN) deal.publish(j);
         __builtin_amdgcn_s_setprio(1);      // as fir_cf32_ols4096_kernel: the second half of a block first
-        dit_back<false>(u, lds, j, tw3);
+        dit_back<false, FOLD>(u, lds, j, tw3);
         // u[q] = conj(y) at time index i = j + 256*bin_of(q).  conj(y[i-1]) sits in lane j-1 of the
         // same register: a wave-shift DPP move brings it over, and only the first lane of each wave
         // needs the last lane of the wave before it (row k-1 for lane 0) -- 64 values through LDS
@@ -815,21 +830,28 @@ int launch_fmchain_cf32_ols4096(const void *in, size_t in_elems, void *out, size
     // too when S == Kov (2048 taps)
     const Gate gate{dyn ? (const unsigned *)gate_word : nullptr, gate_value, S < Kov + 1 ? 2u : 1u};
     if (gated && gate.word) *gated = 1;
-#define PCX_FM_LAUNCH(OCC, NOV, LROWS, CAP)                                                                                      \
+#define PCX_FM_LAUNCH_F(OCC, NOV, LROWS, CAP, FOLD)                                                                               \
     do {                                                                                                                         \
         if (dyn && gate.word)                                                                                                    \
-            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2, true, true>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
+            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2, true, true, FOLD>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
                                in_elems, (float *)out, n_out, (const float2 *)Hspec, (int)Kov, (int)pad, (const float2 *)tw4096,  \
                                nblocks, (const float2 *)prev_in, (float2 *)prev_out, (SchedState *)sched, gate);                  \
         else if (dyn)                                                                                                            \
-            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2, true>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
+            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2, true, false, FOLD>), dim3(CAP), dim3(256), 0, st, (const float2 *)in, \
                                in_elems, (float *)out, n_out, (const float2 *)Hspec, (int)Kov, (int)pad, (const float2 *)tw4096,  \
                                nblocks, (const float2 *)prev_in, (float2 *)prev_out, (SchedState *)sched, gate);                  \
         else                                                                                                                     \
-            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2>), dim3(persistent_grid(nblocks, CAP)), dim3(256), 0, st, \
+            hipLaunchKernelGGL((fmchain_cf32_ols4096_kernel<OCC, NOV, LROWS, SR, 2, false, false, FOLD>), dim3(persistent_grid(nblocks, CAP)), dim3(256), 0, st, \
                                (const float2 *)in, in_elems, (float *)out, n_out, (const float2 *)Hspec, (int)Kov, (int)pad,      \
                                (const float2 *)tw4096, nblocks, (const float2 *)prev_in, (float2 *)prev_out, (SchedState *)nullptr, gate); \
     } while (0)
+    // FOLD: as launch_fir_cf32_ols4096 (PCX_OLS_FOLD=0, diag: the multiply-then-add pair, for A/B)
+#ifdef PCX_DIAG
+    const bool fold = PCX_ENV_INT("PCX_OLS_FOLD", 1) != 0;
+#define PCX_FM_LAUNCH(OCC, NOV, LROWS, CAP) do { if (fold) PCX_FM_LAUNCH_F(OCC, NOV, LROWS, CAP, true); else PCX_FM_LAUNCH_F(OCC, NOV, LROWS, CAP, false); } while (0)
+#else
+#define PCX_FM_LAUNCH(OCC, NOV, LROWS, CAP) PCX_FM_LAUNCH_F(OCC, NOV, LROWS, CAP, true)
+#endif
 #ifdef PCX_DIAG
 #define SR fft4k::kRowsAll
     if (occ == 3) PCX_FM_LAUNCH(3, 8, fft4k::kRowsAll, 768);            // A/B: 3 workgroups per CU, plain loads and stores
@@ -855,6 +877,7 @@ int launch_fmchain_cf32_ols4096(const void *in, size_t in_elems, void *out, size
     else PCX_FM_LAUNCH(4, 8, fft4k::kRowsAll, slots);
 #undef SR
 #undef PCX_FM_LAUNCH
+#undef PCX_FM_LAUNCH_F
     PCX_LAUNCH_CHECK();
     return PCX_OK;
 }

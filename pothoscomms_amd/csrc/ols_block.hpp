@@ -73,6 +73,39 @@ __device__ __forceinline__ void spectrum_times_h(cf (&u)[16], const cf (&v)[16],
         cmul2_conj(u[k0], u[k1], H[k0], H[k1]);
     }
 }
+// The same multiply folded into the inner layer of the inverse's first sixteen-point transform (fft4096.hpp, folded butterflies): every
+// input of that layer's DFT4s is a product conj(X H), so each pair of products and its butterfly take five packed instructions instead
+// of six.  On exit u is where fft16_inner leaves it: what dit_back<.., true> takes.  Register k of the natural order is v[bin_of(k)].
+__device__ __forceinline__ void spectrum_times_h_inner(cf (&u)[16], const cf (&v)[16], const cf (&H)[16])
+{
+#pragma unroll
+    for (int n2 = 0; n2 < 4; n2++) {
+        cf x0 = v[4 * n2], x1 = v[4 * n2 + 1], x2 = v[4 * n2 + 2], x3 = v[4 * n2 + 3];      // v[bin_of(4 n1 + n2)]
+        cf m0, m1;
+        // m0 = conj(h0 x0), t0 = m0 + conj(h2 x2) -> x2, t1 = 2 m0 - t0 -> x0; m1 = conj(h1 x1), t2 = m1 + conj(h3 x3) -> x3, d -> x1;
+        // then the DFT4's four additions in the same block (a compiler-made addition behind it would take a wait state)
+        asm("v_pk_mul_f32 %4, %0, %6" PCX_FOLD_IMC0 "\n\t"
+            "v_pk_mul_f32 %5, %1, %7" PCX_FOLD_IMC0 "\n\t"
+            "v_pk_fma_f32 %4, %0, %6, %4" PCX_FOLD_REC "\n\t"
+            "v_pk_fma_f32 %5, %1, %7, %5" PCX_FOLD_REC "\n\t"
+            "v_pk_fma_f32 %0, %2, %8, %4" PCX_FOLD_IMC "\n\t"
+            "v_pk_fma_f32 %1, %3, %9, %5" PCX_FOLD_IMC "\n\t"
+            "v_pk_fma_f32 %2, %2, %8, %0" PCX_FOLD_REC "\n\t"
+            "v_pk_fma_f32 %3, %3, %9, %1" PCX_FOLD_REC "\n\t"
+            "v_pk_fma_f32 %0, %4, 2.0, %2" PCX_FOLD_2AMP "\n\t"
+            "v_pk_fma_f32 %1, %5, 2.0, %3" PCX_FOLD_2AMP "\n\t"
+            "v_pk_add_f32 %4, %2, %3\n\t"                                                     // t0 + t2
+            "v_pk_add_f32 %2, %2, %3 neg_lo:[0,1] neg_hi:[0,1]\n\t"                           // t0 - t2
+            "v_pk_add_f32 %5, %0, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]\n\t"           // t1 + (-i) d
+            "v_pk_add_f32 %3, %0, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]"               // t1 - (-i) d
+            : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "=&v"(m0), "=&v"(m1)
+            : "v"(H[n2]), "v"(H[4 + n2]), "v"(H[8 + n2]), "v"(H[12 + n2]));
+        u[n2] = m0;
+        u[4 + n2] = m1;
+        u[8 + n2] = x2;
+        u[12 + n2] = x3;
+    }
+}
 // Hb: the lane's bin 0 in the spectrum, the others 256 elements apart -- re-read from L2 in every block
 __device__ __forceinline__ void spectrum_times_h_l2(cf (&u)[16], const cf (&v)[16], const cf *Hb)
 {
